@@ -14,6 +14,11 @@ ranks exchange their per-restart moments once per step (one all-gather, Chan mer
 mrbo/parallel.py).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--ell L | --mle]
+                       [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints one JSON result line (the roofline
+  figures in it come from the timed launches' own HIP events and work counters).  --full adds what
+  takes runs of its own: the CPU baseline (the oracle on the host cores, `cpu_baseline`).
+  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64).
   N > 1 without WORLD_SIZE in the environment: this process starts N ranks itself
   (python -m torch.distributed.run --nproc-per-node N ...) before touching the GPU, and exits
   with their status; under torchrun (WORLD_SIZE set) each rank runs one GPU.
@@ -63,7 +68,15 @@ def parse():
     ap.add_argument("--cost", action="store_true",
                     help="cost-weighted EI with NonUniformCost (cost_functions.jl:5-20; build-defined, "
                          "parity unpinned)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle on "
+                         "the host cores, about --cpu-seconds × 2 of CPU time) as `cpu_baseline` of the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (the rollout's values, "
+                         "gradients, status and work counters, the ETO rows, and x0 / the stop flags after "
+                         "the update) as DIR/<name>.npy, float64; beyond 64 MB in all, a fixed seeded sample "
+                         "of each large array (rank 0, its own shard)")
     ap.add_argument("--schedule", choices=("auto", "index", "longest-first"), default="auto",
                     help="order in which the persistent waves take the trajectories: index order, or "
                          "longest first by the first step's work counters within each of the kernel's "
@@ -195,6 +208,34 @@ def cpu_baseline(pb, M_full, R_full, budget_s, cost=None):
                            "sample": f"first restart x {Ma} MC samples ({dta:.1f} s), {aff} threads = the "
                                      f"process's whole affinity set",
                            "cgroup_cpu_quota": quota})
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> numpy array or device tensor.  Each goes to path/<name>.npy as float64 (the
+    int32 status words and int64 work counters are exact in it).  When all of them together pass
+    DUMP_LIMIT_BYTES, every array above 1 MB is cut to a sample of its flat (C-order) elements at
+    sorted indices drawn from a generator seeded by the array's size alone, so two runs with the
+    same arguments write the same elements."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    nbytes = {k: 8 * int(np.prod(v.shape)) for k, v in arrays.items()}
+    small = sum(b for b in nbytes.values() if b <= 2**20)
+    large = sum(b for b in nbytes.values() if b > 2**20)
+    keep = 1.0 if small + large <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - small) / large
+    for name, v in arrays.items():
+        flat = v.reshape(-1)
+        if keep < 1.0 and nbytes[name] > 2**20:
+            n = flat.shape[0]
+            idx = np.sort(np.random.default_rng(n).integers(0, n, size=int(n * keep)))
+            flat = flat[torch.from_numpy(idx).to(flat.device) if torch.is_tensor(flat) else idx]
+            shape = flat.shape
+        else:
+            shape = tuple(v.shape)
+        a = flat.cpu().numpy() if torch.is_tensor(flat) else np.asarray(flat)
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64).reshape(shape))
 
 
 def main():
@@ -376,7 +417,12 @@ def main():
     if mle:
         res["config"]["mle"] = {"theta": float(mle["theta"][0]), "neg_log_likelihood": float(mle["neg_log_likelihood"]),
                                 "iterations": int(mle["iterations"])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's launch outputs as the device holds them (flat, column-major: values,
+        # grad_theta, status (M, R); grad_x (d, M, R); evals (NCOUNTERS, M, R)), its ETO rows (W, R),
+        # and x0 (d, R) / the stop flags (R) as its update left them
+        dump_outputs(args.dump_outputs, dict(out, eto=last["eto"], x0=x0, active=active))
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(pb, M_local, R, args.cpu_seconds, cost=pb.cost_model())
     if rank == 0:
         print(json.dumps(res), flush=True)

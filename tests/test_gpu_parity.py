@@ -228,6 +228,34 @@ def test_bench_sharded_rccl_one_rank_matches_plain(gpu, tmp_path):
     np.testing.assert_allclose(a["x0"], b["x0"], rtol=1e-14)
 
 
+def test_bench_plain_run_dumps_its_last_step_and_repeats(gpu, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, reports `ms_per_step` and
+    carries no CPU baseline; --dump-outputs writes the last timed step's arrays as float64 .npy
+    files, the ETO rows and x0 among them equal to what --dump records, and a second run with the
+    same arguments writes the same arrays bit for bit."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--restarts", "4", "--config", "C2", "--mc-per-gpu", "64",
+              "--eta", "0.5"]
+    env = {k: v for k, v in os.environ.items() if k != "MRBO_DIST_BACKEND"}
+    a = _bench(common + ["--dump-outputs", str(tmp_path / "a"), "--dump", str(tmp_path / "a.npz")], env)
+    b = _bench(common + ["--dump-outputs", str(tmp_path / "b")], env)
+    for res in (a, b):
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and "cpu_baseline" not in res
+        assert res["unit"] == "trajectories/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+        np.testing.assert_allclose(res["value"], 64 * 4 / (res["ms_per_step"] * 1e-3), rtol=1e-9)
+    T, d = 64 * 4, 2
+    shapes = dict(values=(T,), status=(T,), grad_x=(d * T,), grad_theta=(T,), evals=(5 * T,), x0=(d, 4), active=(4,))
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(list(shapes) + ["eto"])
+    for n in names:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype == np.float64 and (n == "eto" or x.shape == shapes[n])
+        np.testing.assert_array_equal(x, y)
+    assert np.abs(np.load(tmp_path / "a" / "grad_x.npy")).max() > 0      # a launch's results, not zeros
+    z = np.load(tmp_path / "a.npz")
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "eto.npy"), z["eto"])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x0.npy"), z["x0"])
+
+
 def test_bench_two_ranks_rehearsal_matches_one_rank(gpu, tmp_path):
     """`bench.py --gpus 2` starts its two ranks itself (torch.distributed.run) and exchanges the
     per-restart moments once per step; rehearsed on one GPU over gloo (MRBO_DIST_BACKEND=gloo, both

@@ -363,6 +363,34 @@ def test_bench_kernel_label_names_the_profiled_kernel():
     assert any(bench.kernel_label(6, dict(rpl=1, spec=1, fmax=4)) in r["Name"] for r in rows)
 
 
+def test_bench_dump_outputs_writes_float64_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array goes out as float64 under its name and shape (integer
+    status words and counters exactly); past the byte limit the large arrays are cut to a sample
+    of their flat elements that is the same from call to call, the small ones stay whole, and the
+    files together stay within the limit."""
+    import torch
+    import bench
+    big = torch.arange(300000, dtype=torch.int64)
+    arrays = dict(values=np.linspace(0.0, 1.0, 12).reshape(3, 4), status=torch.arange(5, dtype=torch.int32), evals=big)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert all(v.dtype == np.float64 for v in got.values())
+    np.testing.assert_array_equal(got["values"], arrays["values"])
+    np.testing.assert_array_equal(got["status"], np.arange(5.0))
+    np.testing.assert_array_equal(got["evals"], np.arange(300000.0))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2**20 + 1000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), arrays)
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in arrays}
+    c = {k: np.load(tmp_path / "c" / f"{k}.npy") for k in arrays}
+    for k in arrays:
+        np.testing.assert_array_equal(b[k], c[k])
+    np.testing.assert_array_equal(b["values"], arrays["values"])
+    assert 0 < b["evals"].size < 300000 and np.isin(b["evals"], got["evals"]).all()
+    assert (np.diff(b["evals"]) >= 0).all()                 # sorted flat indices of arange
+    assert sum(v.nbytes for v in b.values()) <= 2**20 + 1000
+
+
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc needed")
 def test_every_kernel_unit_matches_the_kparams_layout(tmp_path):
     """Each kernel unit's KernelSet carries sizeof(KParams) from its own compile; mrbo_plan_create

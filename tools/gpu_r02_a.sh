@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-me
   > $out/pytest.log 2>&1
 echo "pytest rc=$?" >> $out/pytest.log
 tail -5 $out/pytest.log
-timeout -k 10 240 python -u bench.py > $out/bench_c3.json 2> $out/bench_c3.err && \
+timeout -k 10 240 python -u bench.py --full > $out/bench_c3.json 2> $out/bench_c3.err && \
 timeout -k 10 120 python -u bench.py --mle --no-cpu-baseline > $out/bench_c3_mle.json 2> $out/bench_c3_mle.err && \
 timeout -k 10 120 python -u bench.py --config C4 --mc-per-gpu 1024 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_c4.json 2> $out/bench_c4.err && \
 timeout -k 10 120 python -u bench.py --config C4 --mc-per-gpu 1024 --steps 3 --warmup 1 --mle --no-cpu-baseline > $out/bench_c4_mle.json 2> $out/bench_c4_mle.err && \

@@ -31,7 +31,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1
       rc=$?; tail -3 "$out/smoke.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$out/bench_c3.json" 2> "$out/bench_c3.err"
+      timeout -k 10 300 python -u bench.py --full > "$out/bench_c3.json" 2> "$out/bench_c3.err"
       rc=$?; tail -c 600 "$out/bench_c3.json" ;;
     rows)
       timeout -k 10 200 python -u bench.py --mle --no-cpu-baseline > "$out/bench_c3_mle.json" 2> "$out/bench_c3_mle.err" && \

@@ -6,7 +6,7 @@ export MRBO_PARITY_REPORT=$out/parity.json
 timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider > $out/pytest.log 2>&1
 rc=$?; tail -3 $out/pytest.log; [ $rc -ne 0 ] && { grep -E "FAILED|Error" $out/pytest.log | head -20; exit $rc; }
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || exit 1
-timeout -k 10 300 python -u bench.py > $out/bench_c3.json 2> $out/bench_c3.err || exit 1
+timeout -k 10 300 python -u bench.py --full > $out/bench_c3.json 2> $out/bench_c3.err || exit 1
 python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'])" $out/bench_c3.json
 L=rollout-bayesian-optimization_amd/mrbo/variants/libmrbo_tail.so
 for rs in 0 1; do

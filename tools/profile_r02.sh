@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out/r02p
 mkdir -p $out
 cd $root
-timeout -k 10 240 python -u bench.py > $out/bench_default.json 2> $out/bench_default.err || exit 1
+timeout -k 10 240 python -u bench.py --full > $out/bench_default.json 2> $out/bench_default.err || exit 1
 bash tools/profile.sh c3_r02 --steps 2 --warmup 1 --no-cpu-baseline || exit 1
 export TMPDIR=/tmp
 row() {  # row <name> <bench args...>
