@@ -35,24 +35,9 @@ enum { COST_NONE = 0, COST_QUADRATIC = 1, COST_LOGLINEAR = 2 };   // mrbo_cost_t
 // N ≤ 256 (L0⁻¹ from L2, four rows per lane): blocks (1,0), (2,0), (2,1) of the block triangle
 // (packed indices 1, 3, 4) are also staged in workgroup LDS, in the LD = 65 layout of the N ≤ 128
 // kernel; their products read LDS instead of L2 (device and host agree through gl_lds_slot).
-// MRBO_GL_LDS_BLOCKS=0: every block from L2.  The chained / streamed A/B variants read L2 only.
-#ifndef MRBO_GL_LDS_BLOCKS
-#define MRBO_GL_LDS_BLOCKS 3
-#endif
-#if defined(MRBO_GL_CHAIN) || defined(MRBO_K1_STREAM)
-constexpr int GL_LDS_BLOCKS = 0;
-#else
-constexpr int GL_LDS_BLOCKS = MRBO_GL_LDS_BLOCKS;
-#endif
+constexpr int GL_LDS_BLOCKS = 3;
 static_assert(GL_LDS_BLOCKS >= 0 && GL_LDS_BLOCKS <= 3, "LDS-resident L2-layout blocks: 0..3");
-#ifdef MRBO_GL_LDS_DIAG
-// A/B: the diagonal blocks (0,0), (1,1), (2,2) instead, walked by the folded LDS products
-constexpr int GL_LDS_B0 = 0, GL_LDS_B1 = 2, GL_LDS_B2 = 5;
-constexpr bool GL_LDS_FOLD = true;
-#else
 constexpr int GL_LDS_B0 = 1, GL_LDS_B1 = 3, GL_LDS_B2 = 4;
-constexpr bool GL_LDS_FOLD = false;
-#endif
 __host__ __device__ constexpr int gl_lds_slot(int b) {
   return (b == GL_LDS_B0 && GL_LDS_BLOCKS > 0) ? 0 : (b == GL_LDS_B1 && GL_LDS_BLOCKS > 1) ? 1
        : (b == GL_LDS_B2 && GL_LDS_BLOCKS > 2) ? 2 : -1;
@@ -158,8 +143,7 @@ __device__ __forceinline__ double djoin(int lo, int hi) {
 // A fresh register pair holding v's bits: ONE v_mov_b64.  v_permlane16/32_swap overwrite both of
 // their operands, so a swap of a double with itself needs two copies of it while it stays live; the
 // compiler made them per dword (two v_mov_b32 per operand, four per double).  TAG makes the two
-// copies distinct asm statements, so that they are not merged into one.  MRBO_NO_DCOPY: the
-// compiler's copies (A/B).
+// copies distinct asm statements, so that they are not merged into one.
 template <int TAG>
 __device__ __forceinline__ double dcopy(double v) {
   double r;
@@ -175,12 +159,8 @@ __device__ __forceinline__ double dcopy(double v) {
 // the explicit copies' fixed live ranges cost spills: C5 + cost scratch 352 → 896 B per lane).
 template <int M, bool KEEP, bool COPY = true>
 __device__ __forceinline__ void self_swap(double v, double& first, double& second) {
-#ifdef MRBO_NO_DCOPY
-  const double c0 = v, c1 = v;
-#else
   const double c0 = (KEEP && COPY) ? dcopy<0>(v) : v;
   const double c1 = COPY ? dcopy<1>(v) : v;
-#endif
   int al, ah, bl, bh;
   dsplit(c0, al, ah);
   dsplit(c1, bl, bh);
@@ -205,13 +185,11 @@ __device__ __forceinline__ void self_swap(double v, double& first, double& secon
 // unrolling) is made by one v_mov_b64 instead of the compiler's two v_mov_b32: the swap overwrites
 // it, so it cannot stay an inline constant.
 __device__ __forceinline__ double swap_operand(double v) {
-#ifndef MRBO_NO_DCOPY
   if (__builtin_constant_p(v) && v == 0.0) {
     double z;
     asm("v_mov_b64 %0, 0" : "=v"(z));
     return z;
   }
-#endif
   return v;
 }
 
@@ -242,18 +220,8 @@ __device__ __forceinline__ void row_blocks(double v, double& blk_p, double& blk_
   self_swap<32, false, COPY>(P ? a1 : a0, blk_p, blk_p2); // [rP ×4], [rP+2 ×4]
 }
 
-// All four blocks at once: one v_permlane16_swap and two v_permlane32_swap per dword (blocks 0, 2
-// from the first pl16 half, 1, 3 from the second) instead of a pl16 + pl32 pair per block pair.
-template <bool COPY = false>
-__device__ __forceinline__ void row_blocks4(double v, double& b0, double& b1, double& b2, double& b3) {
-  double a0, a1;
-  self_swap<16, true, COPY>(v, a0, a1);    // [r0 r0 r2 r2], [r1 r1 r3 r3]
-  self_swap<32, false, COPY>(a0, b0, b2);  // [r0 ×4], [r2 ×4]
-  self_swap<32, false, COPY>(a1, b1, b3);  // [r1 ×4], [r3 ×4]
-}
-
 // The three broadcast operands of a folded product (bcast_fold_fwd / _bwd) in 3 swaps and 2 copies
-// per dword, instead of all four blocks (row_blocks4: 3 swaps, 3 copies) plus a per-row select of
+// per dword, instead of all four blocks (3 swaps, 3 copies) plus a per-row select of
 // the folded pass's operand (2 v_cndmask per double).  With a0 = [r0 r0 r2 r2], a1 = [r1 r1 r3 r3]
 // from the first swap, v_permlane32_swap(a1, a0) gives X = [r1 r1 r0 r0] and Y = [r3 r3 r2 r2]:
 //   forward:  Y is the folded operand (row 1: block 3, rows 2, 3: block 2, row 0 idle) and the
@@ -348,13 +316,9 @@ __device__ __forceinline__ void wave_reduce(double (&v)[K], double* red, int lan
   if constexpr (S < 4) v[0] = fold_all<4>(v[0]);
   if constexpr (S < 5) v[0] = fold_all<2>(v[0]);
   v[0] = fold_all<1>(v[0]);
-#ifndef MRBO_REDUCE_LEADER_STORE
   // every lane of a group holds the same bits and the same idx: an unconditional store keeps the
   // reductions of one phase in one scheduling region (no exec-mask branch between them; C3 −0.3 %)
   red[idx] = v[0];
-#else
-  if ((lane & ((64 >> S) - 1)) == 0) red[idx] = v[0];
-#endif
 }
 
 // wave_reduce within each 32-lane half of the wave (half-wave mode: two trajectories per wave, one
@@ -432,16 +396,12 @@ __device__ __forceinline__ double qnan() { return sconst<0u, 0x7ff80000u>(); }
 // coefficient into a VGPR pair first (two v_mov_b32 per step, three VALU instructions per
 // polynomial term).  The addend is a template constant, so only a lane-uniform value can reach the
 // "s" operand (a per-lane value there would be silently read from lane 0).  Not volatile: the
-// scheduler moves it like any arithmetic.  MRBO_NO_FMA_SC: plain fma (A/B).
+// scheduler moves it like any arithmetic.
 template <unsigned LO, unsigned HI>
 __device__ __forceinline__ double fma_sc(double a, double b) {
-#ifdef MRBO_NO_FMA_SC
-  return fma(a, b, sconst<LO, HI>());
-#else
   double d;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(sconst<LO, HI>()));
   return d;
-#endif
 }
 
 // exp(x), inlined: the device library's algorithm and coefficients in the same operation order
@@ -452,23 +412,6 @@ __device__ __forceinline__ double fexp(double x) {
   const double k = __builtin_rint(x * sconst<0x652b82feu, 0x3ff71547u>());            // x·log2(e)
   double r = fma(sconst<0xfefa39efu, 0xbfe62e42u>(), k, x);                          // − k·ln2_hi
   r = fma(sconst<0x3b39803fu, 0xbc7abc9eu>(), k, r);                                 // − k·ln2_lo
-#ifdef MRBO_EXP_ESTRIN
-  // the same degree-11 polynomial P(r) = Σ c_k r^k (c0 = c1 = 1) in Estrin form: pairs
-  // b_j = c_{2j} + c_{2j+1} r, then q = b + r²·b', then P = q0 + r⁴(q1 + r⁴ q2) -- dependent
-  // depth 5 instead of 11, three more multiplies; not bit-identical to the device library's exp
-  const double r2 = r * r, r4 = r2 * r2;
-  double c10e = sconst<0xfca7ab0cu, 0x3e928af3u>();
-  asm volatile("" : "+v"(c10e));
-  const double b5 = fma(sconst<0x6a5dcb37u, 0x3e5ade15u>(), r, c10e);                 // c10 + c11 r
-  const double b4 = fma_sc<0x7c89e6b0u, 0x3efa0199u>(r, sconst<0x623fde64u, 0x3ec71deeu>());   // c8 + c9 r
-  const double b3 = fma_sc<0x1852b7b0u, 0x3f56c16cu>(r, sconst<0x14761f6eu, 0x3f2a01a0u>());
-  const double b2 = fma_sc<0x555502a1u, 0x3fa55555u>(r, sconst<0x11122322u, 0x3f811111u>());
-  const double b1 = fma_sc<0x0000000bu, 0x3fe00000u>(r, sconst<0x55555511u, 0x3fc55555u>());
-  const double b0 = r + 1.0;
-  const double q2 = fma(b5, r2, b4), q1 = fma(b3, r2, b2), q0 = fma(b1, r2, b0);
-  const double p = fma(fma(q2, r4, q1), r4, q0);
-  double e = __builtin_ldexp(p, (int)k);
-#else
   double c10 = sconst<0xfca7ab0cu, 0x3e928af3u>();
   asm volatile("" : "+v"(c10));   // one of the first step's two constants must live in VGPRs
   double p = fma(sconst<0x6a5dcb37u, 0x3e5ade15u>(), r, c10);
@@ -483,27 +426,16 @@ __device__ __forceinline__ double fexp(double x) {
   p = fma(r, p, 1.0);
   p = fma(r, p, 1.0);
   double e = __builtin_ldexp(p, (int)k);
-#endif
   e = (x > sconst<0u, 0x40900000u>()) ? __builtin_inf() : e;   // x > 1024
   e = (x < sconst<0u, 0xc090cc00u>()) ? 0.0 : e;               // x < −1075
   return e;
 }
 
-// Default (round 5): fexp inlined at every use, the paired xexp2 too.  Round 1 measured no gain from
+// fexp is inlined at every use, the paired xexp2 too (since round 5).  Round 1 measured no gain from
 // inlining (the calls' latency hidden by the second wave, VGPR spills 66 → 93); on the round-5
 // kernel a leaf call costs ≈ 15 v_readlane reloads of spilled SGPRs before every s_swappc, and
-// inlining runs C3 1.2 % faster with the spill count unchanged (6 VGPRs).  MRBO_LEAF_EXP: the
-// round-4 leaf calls (A/B).
-#ifdef MRBO_INLINE_TRANSCENDENTALS
-__device__ __forceinline__ double xexp(double x) { return exp(x); }
-__device__ __forceinline__ double xerfc(double x) { return erfc(x); }
-#elif !defined(MRBO_LEAF_EXP)
+// inlining runs C3 1.2 % faster with the spill count unchanged (6 VGPRs).
 __device__ __forceinline__ double xexp(double x) { return fexp(x); }
-__device__ __attribute__((noinline)) double xerfc(double x) { return erfc(x); }
-#else
-__device__ __attribute__((noinline)) double xexp(double x) { return exp(x); }
-__device__ __attribute__((noinline)) double xerfc(double x) { return erfc(x); }
-#endif
 
 // √s and 1/√s (s > 0) from one hardware reciprocal square root and two Newton–Raphson steps
 // y ← y(1.5 − ½s·y²): ~1 ulp, and a much shorter dependent chain than a correctly rounded
@@ -609,11 +541,7 @@ __device__ __forceinline__ void rad_eval(const Radial& k, double rho2, double& p
 struct Exp2 {
   double a, b;
 };
-#ifndef MRBO_LEAF_EXP
 __device__ __forceinline__ Exp2 xexp2(double a, double b) {
-#else
-__device__ __attribute__((noinline)) Exp2 xexp2(double a, double b) {
-#endif
   Exp2 r;
   r.a = fexp(a);
   r.b = fexp(b);
@@ -660,8 +588,7 @@ __device__ __forceinline__ PhiPair ei_phi_Phi(double z) {
   const double t = (u - 3.5) * b * r, t2 = t * t;
   // even / odd halves of P(t) = Pe(t²) + t·Po(t²), each split once more (Estrin):
   // Pe = Pe_lo(t²) + t¹²·Pe_hi(t²), six-term Horner chains that run side by side (dependent depth
-  // 6 instead of 11; MRBO_NO_ESTRIN: the two plain Horner chains)
-#ifndef MRBO_NO_ESTRIN
+  // 6 instead of 11)
   const double u2 = t2 * t2, u3 = u2 * t2, u6 = u3 * u3;   // u = t²: u⁶ = t¹²
   double pe, po;
   {
@@ -698,39 +625,6 @@ __device__ __forceinline__ PhiPair ei_phi_Phi(double z) {
     const double po_ = fma(u6, po_h, po_l);
     po = po_;
   }
-#else
-  double pe, po;
-  {
-    double pe_ = sconst<0xf1ab7ccbu, 0x3dd09a8bu>();
-    asm volatile("" : "+v"(pe_));
-    pe_ = fma_sc<0x73fda30du, 0x3e06db11u>(t2, pe_);
-    pe_ = fma_sc<0xf4266242u, 0xbe427e42u>(t2, pe_);
-    pe_ = fma_sc<0x1ed381c5u, 0xbe672292u>(t2, pe_);
-    pe_ = fma_sc<0xb901a919u, 0x3ec385e7u>(t2, pe_);
-    pe_ = fma_sc<0x645605dcu, 0xbf066e11u>(t2, pe_);
-    pe_ = fma_sc<0xfbfa9e67u, 0x3f427e65u>(t2, pe_);
-    pe_ = fma_sc<0xc891e642u, 0xbf7143c4u>(t2, pe_);
-    pe_ = fma_sc<0xf77381b3u, 0xbfa8ff5eu>(t2, pe_);
-    pe_ = fma_sc<0x0c35056au, 0xbfbd7683u>(t2, pe_);
-    pe_ = fma_sc<0x284b1971u, 0xbf859e2cu>(t2, pe_);
-    pe_ = fma_sc<0x9a0ee914u, 0x3ff3e0a9u>(t2, pe_);
-    pe = pe_;
-    double po_ = sconst<0x617fb329u, 0xbe1406aau>();
-    asm volatile("" : "+v"(po_));
-    po_ = fma_sc<0xdb5ecc9au, 0x3e4d421du>(t2, po_);
-    po_ = fma_sc<0x3786431fu, 0xbe79e096u>(t2, po_);
-    po_ = fma_sc<0xc09ddffau, 0x3ea42eb1u>(t2, po_);
-    po_ = fma_sc<0x97b263b0u, 0xbecffe87u>(t2, po_);
-    po_ = fma_sc<0x306b92a0u, 0x3ef97053u>(t2, po_);
-    po_ = fma_sc<0x5777da87u, 0xbf1fda8au>(t2, po_);
-    po_ = fma_sc<0xf98105c2u, 0xbf33cf36u>(t2, po_);
-    po_ = fma_sc<0x67477473u, 0x3f938ec6u>(t2, po_);
-    po_ = fma_sc<0x6045eed1u, 0x3fb68610u>(t2, po_);
-    po_ = fma_sc<0xec6b3bb9u, 0x3fb8f702u>(t2, po_);
-    po_ = fma_sc<0x20ea5946u, 0xbfc1ebd2u>(t2, po_);
-    po = po_;
-  }
-#endif
 
   const double P = fma(t, po, pe);
   const double q = 0.5 * E * (P * (a * r));   // ½·E·erfcx(u)
@@ -739,16 +633,6 @@ __device__ __forceinline__ PhiPair ei_phi_Phi(double z) {
   o.Phi = (z > 0.0) ? 1.0 - q : q;
   return o;
 }
-#ifdef MRBO_LIBM_EI   // A/B: the libm pair (two leaf calls)
-__device__ __forceinline__ PhiPair ei_pp(double z) {
-  PhiPair o;
-  o.phi = xexp(-0.5 * (z * z)) * 0.3989422804014327;
-  o.Phi = 0.5 * xerfc(-z * 0.7071067811865476);
-  return o;
-}
-#else
-__device__ __forceinline__ PhiPair ei_pp(double z) { return ei_phi_Phi(z); }
-#endif
 
 // The base decision rule g(μ, σ, θ) and the partials DecisionRule takes by ForwardDiff
 // (decision_rules.jl:23-34), in closed form.
@@ -778,7 +662,7 @@ __device__ __forceinline__ EIp rule_partials(int rule, double mu, double sig, do
   }
   const double imp = fmin - mu - theta;
   const double z = imp * isig;
-  const PhiPair pp = ei_pp(z);
+  const PhiPair pp = ei_phi_Phi(z);
   const double phi = pp.phi, Phi = pp.Phi;
   const double pis = phi * isig;
   if (rule == RULE_POI) {

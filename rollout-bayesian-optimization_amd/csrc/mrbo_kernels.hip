@@ -38,7 +38,7 @@ constexpr bool has_spec(int d, int rpl) { return d <= 8 && rpl <= 4; }
 // units of d ≤ 4, Matérn-5/2 + EI (C1, C2)
 // Matérn-5/2 + EI + the quadratic NonUniformCost fixed at compile time, rollout_kernel<D, RPL, 2>:
 // the FMAX = 6 units of d ≤ 8 at N = 65..256 (C5 --cost); other cost plans run the generic kernel
-#if MRBO_FMAX == 6 && MRBO_D <= 8 && !defined(MRBO_AB_MIN) && !defined(MRBO_NO_COST_SPEC)
+#if MRBO_FMAX == 6 && MRBO_D <= 8 && !defined(MRBO_AB_MIN)
 #define MRBO_HAS_COST 1
 #else
 #define MRBO_HAS_COST 0

@@ -13,17 +13,10 @@
 #include <utility>
 
 #include "mrbo_device.h"
-#ifdef MRBO_BCAST_HEADER   // A/B: an alternative generated header (tools/gen_bcast_asm.py BCAST_OUT=…)
-#include MRBO_BCAST_HEADER
-#else
 #include "bcast_asm.h"
-#endif
 
 #ifndef MRBO_WAVES_PER_SIMD
 #define MRBO_WAVES_PER_SIMD 2
-#endif
-#ifndef MRBO_HESS16   // 1: the Hessian reduction's tail chunk as a 16-value reduction (A/B)
-#define MRBO_HESS16 0
 #endif
 // Everything below is compiled per fantasy capacity FMAX (-DMRBO_FMAX, default 6 = h ≤ 5; the
 // kernel units are also built with FMAX = 4 for h ≤ 3): an inline namespace per FMAX keeps the
@@ -39,17 +32,6 @@ namespace mrbo {
 inline namespace MRBO_FNS {
 
 constexpr double PAD_FAR = 1e100;   // coordinate of padded data rows (WaveCtx::rowv)
-
-// MRBO_SQ_EAGER (A/B, not the default): the eager all-column value pass of the square layout
-// (Lay::SQ_EAGER).  Measured neutral (C3 −0.3 %, C3-MLE +0.2 %, within the spread) while it issues
-// 4 % more VALU per wave: about half of C3's non-batched value passes are NOT followed by a GRADC
-// pass (the iteration converges on x_tol / f_tol after an accepted trial), and their extra columns
-// are wasted work.
-#ifdef MRBO_SQ_EAGER
-constexpr bool SQ_EAGER_ON = true;
-#else
-constexpr bool SQ_EAGER_ON = false;
-#endif
 
 template <int D, int RPL, int HW = 1>
 struct Lay {
@@ -119,11 +101,7 @@ struct Lay {
   static constexpr int U_SIZE = ((U_KC + 15) + 1) & ~1;
   static constexpr int G12 = 3 * NRL;                    // per-lane [g1, g2, Y0] of the base rows
   static constexpr int EC = SQ ? (2 * FMAX + 1) * NRL : 0;  // E (FMAX×NRL) + C ((FMAX+1)×NRL) in LDS
-  // SQ_EAGER (the square layout of the FMAX = 4 units, full-wave): the value pass runs all D1
-  // columns of the forward product and stashes columns 1..d here for the GRADC pass that follows
-  static constexpr bool SQ_EAGER = SQ_EAGER_ON && SQ && HW == 1 && FMAX <= 4;
-  static constexpr int STASH = SQ_EAGER ? D * NRL : 0;
-  static constexpr int WAVE_LDS = BROWS * BS + REDN + U_SIZE + G12 + EC + STASH;
+  static constexpr int WAVE_LDS = BROWS * BS + REDN + U_SIZE + G12 + EC;
   // L0⁻¹ in LDS, shared by the waves of a workgroup.  BC: dense zero-padded 64×64 blocks,
   // column-major with odd leading dimension LD = 65, so the column walk (forward product,
   // lane i reads [i][j]) and the row walk (backward product, lane i reads [k][i]) are both
@@ -216,7 +194,10 @@ struct WaveCtx {
   double* E;            // LDS (SQ) or global: FMAX × NR  inverse-factor fantasy rows (base columns)
   double* C;            // LDS (SQ) or global: (FMAX+1) × NR  base part of c for surfaces -1..h
   double* SUMS;         // packed layouts: global [64][8] per-start sums of the batched start pass
-  double* STASH;        // L2-fed layouts (GL): global [RPL][D][64] gradient columns of the last value pass
+  // never read or written: the eager value passes that used it are gone, but without
+  // this member and its assignment in wave_setup the compiler allocates the registers of the
+  // N ≤ 256 kernels differently, so it leaves in a change of its own, with a benchmark
+  double* STASH;
   double X0[RPL][D];    // own base rows
   bool valid[RPL];
   int N, Npad;
@@ -226,27 +207,8 @@ struct WaveCtx {
   // every non-periodic radial function and both derivative factors are exactly 0 (exp underflows),
   // and their c, w, E, P entries are 0 as well -- so for those kernels no select is needed: true at
   // compile time in the Matérn-5/2 specialisation.  The Periodic kernel keeps the per-row mask.
-  // base covariate a of row slot s.  MRBO_X0_GLOBAL (A/B, N ≤ 256 layout): read from the L2-resident
-  // device copy at each use instead of holding 4·d registers per lane across the trajectory
-  __device__ __forceinline__ double x0(const KParams& kp, int s, int a) const {
-#ifdef MRBO_X0_GLOBAL
-    if constexpr (Ly::GL) {
-      const double v = kp.X0[(long long)a * Ly::NR + lane + WAVE * s];
-#ifndef MRBO_NO_PAD_FAR
-      return (valid[s] || kp.kernel == KERNEL_PERIODIC) ? v : PAD_FAR;
-#else
-      return v;
-#endif
-    }
-#endif
-    return X0[s][a];
-  }
   __device__ __forceinline__ bool rowv(const KParams& kp, int s) const {
-#ifdef MRBO_NO_PAD_FAR
-    return valid[s];
-#else
     return kp.kernel != KERNEL_PERIODIC ? true : valid[s];
-#endif
   }
   // opaque lane index (see evaluate): per-lane addresses are rematerialised where used
   __device__ __forceinline__ int ln() const {
@@ -373,20 +335,6 @@ __device__ __forceinline__ const double (&tail8(const double (&a)[K]))[K - 8] {
   return *reinterpret_cast<const double(*)[K - 8]>(&a[8]);
 }
 
-// One 16-step block of a register-broadcast product.  MRBO_K1_SPLIT: K = 1 (the value product
-// L0⁻¹kx and the backward w = L0⁻ᵀY0) with two accumulators over the even and odd steps -- measured
-// 0.6 % SLOWER on C3 (round 5: the chain is not what the product waits on), so off by default.
-template <int K, int STRIDE>
-__device__ __forceinline__ void bcast_run(double (&acc)[K], const double (&bq)[K], unsigned addr) {
-#ifdef MRBO_K1_SPLIT
-  if constexpr (K == 1) {
-    BcastAsmSplit<STRIDE>::run(acc, bq, addr);
-    return;
-  }
-#endif
-  BcastAsm<K, STRIDE>::run(acc, bq, addr);
-}
-
 // COPY: the row replication's operand copies as v_mov_b64 (self_swap); false for the 512-register
 // L2-fed kernels' LDS-resident blocks (gl_block), where they cost spills
 template <int K, int JSTRIDE, int HW = 1, bool COPY = true>
@@ -406,7 +354,7 @@ __device__ __forceinline__ void bcast_product_k(double (&acc)[K], const double (
         self_swap<16, true>(v[c], b0, b1);
         bp[c] = p == 0 ? b0 : b1;
       }
-      bcast_run<K, 8 * JSTRIDE>(acc, bp, a0 + 8u * 16u * p * JSTRIDE);
+      BcastAsm<K, 8 * JSTRIDE>::run(acc, bp, a0 + 8u * 16u * p * JSTRIDE);
     }
     return;
   }
@@ -419,8 +367,8 @@ __device__ __forceinline__ void bcast_product_k(double (&acc)[K], const double (
       if (p == 0) row_blocks<0, COPY>(v[c], bp[c], bp2[c]);
       else row_blocks<1, COPY>(v[c], bp[c], bp2[c]);
     }
-    bcast_run<K, 8 * JSTRIDE>(acc, bp, a0 + 8u * 16u * p * JSTRIDE);
-    if (16 * (p + 2) < nrows) bcast_run<K, 8 * JSTRIDE>(acc, bp2, a0 + 8u * 16u * (p + 2) * JSTRIDE);
+    BcastAsm<K, 8 * JSTRIDE>::run(acc, bp, a0 + 8u * 16u * p * JSTRIDE);
+    if (16 * (p + 2) < nrows) BcastAsm<K, 8 * JSTRIDE>::run(acc, bp2, a0 + 8u * 16u * (p + 2) * JSTRIDE);
   }
 }
 
@@ -472,27 +420,14 @@ __device__ __forceinline__ void bcast_fold_fwd_k(double (&acc)[K], const double 
   double b0[K], b1[K], m[K], f[K];
 #pragma unroll
   for (int c = 0; c < K; ++c) {
-#ifdef MRBO_FOLD_SELECT   // round-5 first form: all four blocks, then a per-row select
-    double b2, b3;
-    row_blocks4<true>(v[c], b0[c], b1[c], b2, b3);
-    m[c] = (q == 1) ? b3 : b2;
-#else
     fold_blocks(v[c], true, b0[c], b1[c], m[c]);
-#endif
     f[c] = 0.0;
   }
   // row 1: (48 + t, 48 + n) = own address + 32 + 16·LD; row 0: the zeros (15, 33 + n); rows 2, 3: block 2
   const unsigned a3 = (q == 1) ? a0 + 8u * (48u * LD + 32u) : (q == 0) ? lds_addr(Lsq + 33 * LD + 15) : a0 + 8u * 32u * LD;
-#ifdef MRBO_FOLD3_MERGED   // A/B: +1.2 % on C3 (round 5), so off
-  if constexpr (K == 1) {   // the three passes in one software-pipelined statement
-    BcastAsm3<8 * LD>::run(acc, f, b0, b1, m, a0, a3);
-  } else
-#endif
-  {
-    bcast_run<K, 8 * LD>(acc, b0, a0);
-    bcast_run<K, 8 * LD>(acc, b1, a0 + 8u * 16u * LD);
-    bcast_run<K, 8 * LD>(f, m, a3);
-  }
+  BcastAsm<K, 8 * LD>::run(acc, b0, a0);
+  BcastAsm<K, 8 * LD>::run(acc, b1, a0 + 8u * 16u * LD);
+  BcastAsm<K, 8 * LD>::run(f, m, a3);
   fold_finish<K>(acc, f, true);
 }
 
@@ -505,27 +440,14 @@ __device__ __forceinline__ void bcast_fold_bwd_k(double (&acc)[K], const double 
   double b2[K], b3[K], m[K], f[K];
 #pragma unroll
   for (int c = 0; c < K; ++c) {
-#ifdef MRBO_FOLD_SELECT
-    double b0, b1;
-    row_blocks4<true>(v[c], b0, b1, b2[c], b3[c]);
-    m[c] = (q == 2) ? b0 : b1;
-#else
     fold_blocks(v[c], false, b2[c], b3[c], m[c]);
-#endif
     f[c] = 0.0;
   }
   // row 2: (n, t) of output row t = lane − 32; row 3: the zeros (17 + n, 63); rows 0, 1: block 1
   const unsigned a3 = (q == 2) ? lds_addr(Lsq + (lane - 32) * LD) : (q == 3) ? lds_addr(Lsq + 63 * LD + 17) : a0 + 8u * 16u;
-#ifdef MRBO_FOLD3_MERGED
-  if constexpr (K == 1) {   // blocks 2 then 3 (at +16 steps), then the folded pass, in one statement
-    BcastAsm3<8>::run(acc, f, b2, b3, m, a0 + 8u * 32u, a3);
-  } else
-#endif
-  {
-    bcast_run<K, 8>(acc, b3, a0 + 8u * 48u);
-    bcast_run<K, 8>(acc, b2, a0 + 8u * 32u);
-    bcast_run<K, 8>(f, m, a3);
-  }
+  BcastAsm<K, 8>::run(acc, b3, a0 + 8u * 48u);
+  BcastAsm<K, 8>::run(acc, b2, a0 + 8u * 32u);
+  BcastAsm<K, 8>::run(f, m, a3);
   fold_finish<K>(acc, f, false);
 }
 
@@ -553,14 +475,13 @@ __device__ __forceinline__ void bcast_fold_bwd(double (&acc)[K], const double (&
 // chunks of 16, the last one in the smallest power of two that holds it -- a wave_reduce<K> costs
 // ≈ K + log2(64/K) exchanges, so a chunk of 6 values in wave_reduce<8> saves ≈ 30 VALU against
 // wave_reduce<16> (the Hessian's tail chunk: C3 −1 %).  Slots t ≥ n of a chunk hold junk.  t is a
-// compile-time constant in every call of fill.  MRBO_REDUCE16: every chunk of 16 (A/B).
+// compile-time constant in every call of fill.
 template <int HW, int CH, class F>
 __device__ __forceinline__ void wave_reduce_n(F&& fill, int n, double* red, int lane) {
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) {
     const int rem = n - 16 * ch;
     if (rem <= 0) break;
-#ifndef MRBO_REDUCE16
     if (rem <= 2) {
       double v[2];
 #pragma unroll
@@ -576,9 +497,7 @@ __device__ __forceinline__ void wave_reduce_n(F&& fill, int n, double* red, int 
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = fill(16 * ch + q);
       hw_reduce<HW, 8>(v, red + 16 * ch, lane);
-    } else
-#endif
-    {
+    } else {
       double v[16];
 #pragma unroll
       for (int q = 0; q < 16; ++q) v[q] = fill(16 * ch + q);
@@ -586,12 +505,6 @@ __device__ __forceinline__ void wave_reduce_n(F&& fill, int n, double* red, int 
     }
   }
 }
-
-#ifdef MRBO_NO_FOLD
-constexpr bool FOLD = false;
-#else
-constexpr bool FOLD = true;
-#endif
 
 // The same product with this lane's L entries from global memory (L2-resident image):
 // step n of the block at lb[n·64].  All 64 steps of both row blocks of a pass are loaded into
@@ -624,131 +537,6 @@ __device__ __forceinline__ void gl_bcast_product_k(double (&acc)[K], const doubl
   }
 }
 
-// Rows 16q..16q+15 of the 64×64 L2 block at lb (lane offset applied): 16 loads into l.
-__device__ __forceinline__ void gl_load_q(double (&l)[16], const double* lb, int q) {
-#pragma unroll
-  for (int u = 0; u < 16; ++u) l[u] = lb[(16 * q + u) * WAVE];
-}
-
-template <int K>
-__device__ __forceinline__ void gl_quarter(double (&acc)[K], const double (&b)[K], const double (&l)[16]) {
-  if constexpr (K > 9) {
-    gl_quarter<8>(head8(acc), head8(b), l);
-    gl_quarter<K - 8>(tail8(acc), tail8(b), l);
-  } else {
-    BcastRegAsm<K, 0>::run(acc, b, head8(l));
-    BcastRegAsm<K, 8>::run(acc, b, tail8(l));
-  }
-}
-
-// The blocks t = t0..t1 of one row slot as ONE software-pipelined chain (MRBO_GL_CHAIN): the same
-// quarters in the same order as gl_bcast_product (rows 0-15, 32-47, 16-31, 48-63 of each block,
-// blocks in t order: bit-identical sums), with two 16-row buffers -- each quarter's loads are
-// issued one quarter ahead, the next block's first two quarters during this block's last two.
-// gl_bcast_product waits for all 32 rows of a half-block before its first FMA, and the inline
-// FMA blocks are scheduling barriers, so at one wave per SIMD that L2 round trip was exposed
-// twice per block.  lb[t]: block base (lane offset applied), nr[t] = min(64, N − 64t).
-template <int K, int NT>
-__device__ __forceinline__ void gl_chain(double (&acc)[K], const double (&v)[NT][K], const double* const (&lb)[NT],
-                                         const int (&nr)[NT], int t0, int t1) {
-  double la[16], lc[16];
-  gl_load_q(la, lb[t0], 0);
-  if (nr[t0] > 32) gl_load_q(lc, lb[t0], 2);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    if (t < t0 || t > t1 || nr[t] <= 0) continue;
-    double b0[K], b2[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) row_blocks<0>(v[t][c], b0[c], b2[c]);
-    gl_quarter<K>(acc, b0, la);                              // rows 0-15
-    if (nr[t] > 16) gl_load_q(la, lb[t], 1);
-    if (nr[t] > 32) gl_quarter<K>(acc, b2, lc);             // rows 32-47
-    if (nr[t] > 48) gl_load_q(lc, lb[t], 3);
-    double b1[K], b3[K];
-#pragma unroll
-    for (int c = 0; c < K; ++c) row_blocks<1>(v[t][c], b1[c], b3[c]);
-    if (nr[t] > 16) gl_quarter<K>(acc, b1, la);             // rows 16-31
-    const bool more = t + 1 <= t1 && t + 1 < NT && nr[t + 1 < NT ? t + 1 : t] > 0;
-    if (more) gl_load_q(la, lb[t + 1 < NT ? t + 1 : t], 0);
-    if (nr[t] > 48) gl_quarter<K>(acc, b3, lc);             // rows 48-63
-    if (more && nr[t + 1 < NT ? t + 1 : t] > 32) gl_load_q(lc, lb[t + 1 < NT ? t + 1 : t], 2);
-  }
-}
-
-// The single-column (K = 1) products over the L2 blocks -- the value pass's forward product and
-// the backward w = L0⁻ᵀY0 -- as ONE stream of 16-row quarters with MRBO_K1_NB − 1 quarters of
-// loads in flight (MRBO_K1_STREAM).  A K = 1 quarter is 16 dependent FMAs, far shorter than an L2
-// round trip at one wave per SIMD, so gl_bcast_product<1> waited on every half-block's loads.
-// Same quarters, same order, same single accumulation chain per row slot: bit-identical sums.
-// FWD: out[s] = Σ_{t ≤ s} L0⁻¹(s,t) v[t] from the forward copy; else out[s] = Σ_{t ≥ s} of the
-// backward copy's block (t,s) times v[t].  base: the copy's first block, lane offset applied.
-#ifndef MRBO_K1_NB
-#define MRBO_K1_NB 4
-#endif
-template <int RPL, bool FWD>
-struct K1Seq {
-  static constexpr int NP = RPL * (RPL + 1) / 2, NQ = 4 * NP;
-  // pair p → (s, t): FWD s-major with t = 0..s; backward s-major with t = s..RPL-1
-  static constexpr int ps(int p) {
-    int s = 0;
-    for (;;) {
-      const int n = FWD ? s + 1 : RPL - s;
-      if (p < n) return s;
-      p -= n;
-      ++s;
-    }
-  }
-  static constexpr int pt(int p) {
-    int s = 0;
-    for (;;) {
-      const int n = FWD ? s + 1 : RPL - s;
-      if (p < n) return FWD ? p : s + p;
-      p -= n;
-      ++s;
-    }
-  }
-  static constexpr int blk(int p) {   // block index of pair p in the packed block triangle
-    const int s = ps(p), t = pt(p);
-    return FWD ? s * (s + 1) / 2 + t : t * (t + 1) / 2 + s;
-  }
-  static constexpr int qrow(int i) { return (i & 1) * 2 + ((i >> 1) & 1); }   // quarters 0, 2, 1, 3
-  static constexpr bool last_of_s(int p) { return p + 1 == NP || ps(p + 1) != ps(p); }
-};
-
-template <int RPL, bool FWD>
-__device__ __forceinline__ void gl_k1_stream(double (&out)[RPL], const double (&v)[RPL], const double* base, int N) {
-  using S = K1Seq<RPL, FWD>;
-  constexpr int NB = MRBO_K1_NB;
-  double rb[RPL][4];   // row blocks 0..3 of v[t], broadcast to every 16-lane row
-#pragma unroll
-  for (int t = 0; t < RPL; ++t) row_blocks4(v[t], rb[t][0], rb[t][1], rb[t][2], rb[t][3]);
-  double buf[NB][16];
-  auto load = [&](double (&l)[16], int i) {
-    const double* lb = base + (long long)S::blk(i >> 2) * WAVE * WAVE + 16 * S::qrow(i & 3) * WAVE;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) l[u] = lb[u * WAVE];
-  };
-#pragma unroll
-  for (int j = 0; j < NB - 1; ++j)
-    if (j < S::NQ) load(buf[j], j);
-  double acc[1] = {0.0};
-#pragma unroll
-  for (int i = 0; i < S::NQ; ++i) {
-    if (i + NB - 1 < S::NQ) load(buf[(i + NB - 1) % NB], i + NB - 1);
-    const int p = i >> 2, q = S::qrow(i & 3), t = S::pt(p);
-    const int nr = N - WAVE * t;
-    if (16 * q < nr) {
-      const double b[1] = {rb[t][q]};
-      BcastRegAsm<1, 0>::run(acc, b, head8(buf[i % NB]));
-      BcastRegAsm<1, 8>::run(acc, b, tail8(buf[i % NB]));
-    }
-    if ((i & 3) == 3 && S::last_of_s(p)) {
-      out[S::ps(p)] = acc[0];
-      acc[0] = 0.0;
-    }
-  }
-}
-
 template <int K>
 __device__ __forceinline__ void gl_bcast_product(double (&acc)[K], const double (&v)[K], const double* lb, int nrows) {
   if constexpr (K > 9) {
@@ -769,14 +557,8 @@ __device__ __forceinline__ void gl_block(double (&acc)[K], const double (&v)[K],
   const int li = NLB > 0 ? gl_lds_slot(b) : -1;
   if (li >= 0) {
     const double* sq = LinvL + (long long)li * WAVE * LD;
-    if (GL_LDS_FOLD) {   // a diagonal block: the folded three-pass products of the N ≤ 64 kernel
-      if (fwd) bcast_fold_fwd<K>(acc, v, sq, lane);
-      else bcast_fold_bwd<K>(acc, v, sq, lane);
-    } else if (fwd) {
-      bcast_product<K, LD, 1, false>(acc, v, sq + lane, nrows);
-    } else {
-      bcast_product<K, 1, 1, false>(acc, v, sq + lane * LD, nrows);
-    }
+    if (fwd) bcast_product<K, LD, 1, false>(acc, v, sq + lane, nrows);
+    else bcast_product<K, 1, 1, false>(acc, v, sq + lane * LD, nrows);
   } else {
     gl_bcast_product<K>(acc, v, Lg + (long long)b * WAVE * WAVE + lane, nrows);
   }
@@ -839,7 +621,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   for (int s = 0; s < RPL; ++s) {
     double r[D], rho2 = 0.0;
 #pragma unroll
-    for (int a = 0; a < D; ++a) { r[a] = x[a] - W.x0(kp, s, a); rho2 = fma(r[a], r[a], rho2); }
+    for (int a = 0; a < D; ++a) { r[a] = x[a] - W.X0[s][a]; rho2 = fma(r[a], r[a], rho2); }
     if (rows_kept) {
       const double g1 = W.G12[3 * (lane + WAVE * s)];
       const bool v = W.rowv(kp, s);
@@ -849,7 +631,6 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       continue;
     }
     double psi, g1, g2;
-#ifndef MRBO_NO_PAIRED_RAD
     if constexpr (RPL == 1) {
       // this lane's fantasy row (lanes < nf) shares the radial evaluation of its base row
       const int fl = lane < nf ? lane : 0;
@@ -857,9 +638,9 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
 #pragma unroll
       for (int a = 0; a < D; ++a) { rf[a] = x[a] - U[Ly::U_XF + fl * D + a]; rho2f = fma(rf[a], rf[a], rho2f); }
       rad_eval2(W.rad, rho2, rho2f, psi, g1, g2, psif, g1f, g2f);
-    } else
-#endif
-    rad_eval(W.rad, rho2, psi, g1, g2);
+    } else {
+      rad_eval(W.rad, rho2, psi, g1, g2);
+    }
     const bool v = W.rowv(kp, s);
     Bown[s][0] = v ? psi : 0.0;
 #pragma unroll
@@ -869,16 +650,13 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   }
   if (lane < nf && !rows_kept) {  // fantasy rows B[N + r]; [x − X_r, g1, g2] kept for the Hessian
     double r[D], psi, g1, g2;
-#ifndef MRBO_NO_PAIRED_RAD
     if constexpr (RPL == 1) {
 #pragma unroll
       for (int a = 0; a < D; ++a) r[a] = rf[a];
       psi = psif;
       g1 = g1f;
       g2 = g2f;
-    } else
-#endif
-    {
+    } else {
       double rho2 = 0.0;
 #pragma unroll
       for (int a = 0; a < D; ++a) { r[a] = x[a] - U[Ly::U_XF + lane * D + a]; rho2 = fma(r[a], r[a], rho2); }
@@ -909,29 +687,17 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     // broadcast from register slot t.  Row slot s sums block columns t = 0..s in order.
     auto nrows = [&](int t) { const int n = N - WAVE * t; return n < WAVE ? n : WAVE; };
     // RPL = 1 with N > 48: the folded three-pass products (bcast_fold_fwd / _bwd)
-    const bool fold = FOLD && Ly::SQ && HW == 1 && N > 48;
-    // N ≤ 128 (two rows per lane): the diagonal blocks (s, s) by the same folded products
-    // (MRBO_BC_DIAG_FOLD, A/B)
+    const bool fold = Ly::SQ && HW == 1 && N > 48;
+    // MRBO_BC_DIAG_FOLD (N ≤ 128, two rows per lane: the diagonal blocks (s, s) by the same folded
+    // products) was measured neutral and is not built or tested.  The switch is kept
+    // only because without its constant-false arms below the compiler orders two register
+    // definitions of these kernels differently; it goes with WaveCtx::STASH in a change of its own
 #ifdef MRBO_BC_DIAG_FOLD
     constexpr bool DFOLD = !Ly::SQ && HW == 1;
 #else
     constexpr bool DFOLD = false;
 #endif
-    if (Ly::SQ_EAGER && mode == EV_VALUE) {
-      // The K = 1 value product is bound by LDS reads (one ds_read_b64 per FMA, eight waves on
-      // one LDS); ≈ 95 % of C3's non-batched value passes are followed by a GRADC pass at the same
-      // x.  So the value pass runs all D1 columns (seven FMAs per read) and stashes columns 1..d
-      // in the wave's LDS, where the GRADC pass reads them instead of its K = d product.  Same
-      // fold, same steps per column: bit-identical sums.  Off by default (SQ_EAGER_ON above).
-      if (fold) bcast_fold_fwd<D1>(acc[0], Bown[0], W.Linv, lane);
-      else bcast_product<D1, Ly::LD, HW>(acc[0], Bown[0], W.Linv + lane, nrows(0));
-#pragma unroll
-      for (int a = 0; a < D; ++a) W.STASH[a * WAVE + lane] = acc[0][1 + a];
-    } else if (Ly::SQ_EAGER && mode == EV_GRADC) {
-#pragma unroll
-      for (int a = 0; a < D; ++a) acc[0][1 + a] = W.STASH[a * WAVE + lane];
-      acc[0][0] = W.G12[3 * lane + 2];
-    } else if (mode == EV_VALUE) {
+    if (mode == EV_VALUE) {
 #pragma unroll
       for (int s = 0; s < RPL; ++s) {
         double a1[1] = {0.0};
@@ -979,90 +745,8 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     // GL (N ≤ 256): the same register broadcast with L0⁻¹ from L2: lane i reads (i, j) of block
     // (s,t) at blk(s,t)·4096 + j·64 + i, 16 steps' entries loaded ahead into registers
     auto nrows = [&](int t) { const int n = N - WAVE * t; return n < WAVE ? n : WAVE; };
-    const double* L0 = W.Linv + lane;
-#ifdef MRBO_GL_CHAIN
-    int nr[RPL];
-#pragma unroll
-    for (int t = 0; t < RPL; ++t) nr[t] = nrows(t);
+    const double* L0 = W.Linv + lane;   // unused, as LT below: kept for identical device code (WaveCtx::STASH)
     if (mode == EV_VALUE) {
-      double v1[RPL][1];
-#pragma unroll
-      for (int t = 0; t < RPL; ++t) v1[t][0] = Bown[t][0];
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) {
-        const double* lb[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) lb[t] = L0 + Ly::blk(s, t <= s ? t : s) * WAVE * WAVE;
-        double a1[1] = {0.0};
-        gl_chain<1, RPL>(a1, v1, lb, nr, 0, s);
-        acc[s][0] = a1[0];
-      }
-    } else if (mode == EV_GRADC) {
-      double vg[RPL][D];
-#pragma unroll
-      for (int t = 0; t < RPL; ++t)
-#pragma unroll
-        for (int a = 0; a < D; ++a) vg[t][a] = Bown[t][1 + a];
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) {
-        const double* lb[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) lb[t] = L0 + Ly::blk(s, t <= s ? t : s) * WAVE * WAVE;
-        double ag[D];
-#pragma unroll
-        for (int a = 0; a < D; ++a) ag[a] = 0.0;
-        gl_chain<D, RPL>(ag, vg, lb, nr, 0, s);
-#pragma unroll
-        for (int a = 0; a < D; ++a) acc[s][1 + a] = ag[a];
-        acc[s][0] = W.G12[3 * (lane + WAVE * s) + 2];
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) {
-        const double* lb[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) lb[t] = L0 + Ly::blk(s, t <= s ? t : s) * WAVE * WAVE;
-        gl_chain<D1, RPL>(acc[s], Bown, lb, nr, 0, s);
-      }
-    }
-#else
-    // MRBO_GL_EAGER (A/B, not the default): with NonUniformCost ≈ 54 % of C5 + cost's value
-    // passes are followed by a gradient pass at the same x, so the value pass could run all D1
-    // columns and stash columns 1..d in the wave's global slot for that GRADC pass (same blocks,
-    // same rows in the same order per column: bit-identical sums).  Measured (round 6, C5 + cost
-    // 256 × 128, same box): 1 278 → 1 386 ms, +8.5 % -- at one wave per SIMD the nine-column
-    // walk costs far more than the L0⁻¹ stream it saves.
-#ifdef MRBO_GL_EAGER
-    const bool eager = kp.cost != COST_NONE;
-#else
-    const bool eager = false;
-#endif
-    if (mode == EV_VALUE && eager) {
-#pragma unroll
-      for (int s = 0; s < RPL; ++s)
-#pragma unroll
-        for (int t = 0; t <= s; ++t)
-          gl_block<D1, Ly::LD, Ly::NLB>(acc[s], Bown[t], W.Linv, W.LinvL, Ly::blk(s, t), true, lane, nrows(t));
-#pragma unroll
-      for (int s = 0; s < RPL; ++s)
-#pragma unroll
-        for (int a = 0; a < D; ++a) W.STASH[(long long)(s * D + a) * WAVE + lane] = acc[s][1 + a];
-    } else if (mode == EV_GRADC && eager) {
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) {
-#pragma unroll
-        for (int a = 0; a < D; ++a) acc[s][1 + a] = W.STASH[(long long)(s * D + a) * WAVE + lane];
-        acc[s][0] = W.G12[3 * (lane + WAVE * s) + 2];
-      }
-    } else if (mode == EV_VALUE) {
-#ifdef MRBO_K1_STREAM
-      double v1[RPL], o1[RPL];
-#pragma unroll
-      for (int t = 0; t < RPL; ++t) v1[t] = Bown[t][0];
-      gl_k1_stream<RPL, true>(o1, v1, L0, N);
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) acc[s][0] = o1[s];
-#else
 #pragma unroll
       for (int s = 0; s < RPL; ++s) {
         double a1[1] = {0.0};
@@ -1073,7 +757,6 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
         }
         acc[s][0] = a1[0];
       }
-#endif
     } else if (mode == EV_GRADC) {
 #pragma unroll
       for (int s = 0; s < RPL; ++s) {
@@ -1098,7 +781,6 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
         for (int t = 0; t <= s; ++t)
           gl_block<D1, Ly::LD, Ly::NLB>(acc[s], Bown[t], W.Linv, W.LinvL, Ly::blk(s, t), true, lane, nrows(t));
     }
-#endif
   }
 
   if (do_val) {   // Y0 kept for a deferred GRADC / BACK evaluation
@@ -1347,8 +1029,8 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       // lane i (row slot s) reads L0⁻¹[64t+k][64s+i] at blk(t,s)·BLK + i·LD + k for block rows
       // t = s..RPL-1; rows k of Y are broadcast from register slot t
       auto nrows = [&](int t) { const int n = N - WAVE * t; return n < WAVE ? n : WAVE; };
-      const bool fold = FOLD && Ly::SQ && HW == 1 && N > 48;
-#ifdef MRBO_BC_DIAG_FOLD
+      const bool fold = Ly::SQ && HW == 1 && N > 48;
+#ifdef MRBO_BC_DIAG_FOLD   // kept for identical device code only, see the forward product
       constexpr bool DFOLD = !Ly::SQ && HW == 1;
 #else
       constexpr bool DFOLD = false;
@@ -1385,41 +1067,6 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       // blk(t,s)·4096 + k·64 + i; rows k of Y from register slot t
       auto nrows = [&](int t) { const int n = N - WAVE * t; return n < WAVE ? n : WAVE; };
       const double* LT = W.LinvT + lane;
-#ifdef MRBO_GL_CHAIN
-      int nr[RPL];
-#pragma unroll
-      for (int t = 0; t < RPL; ++t) nr[t] = nrows(t);
-      double y1[RPL][1];
-#pragma unroll
-      for (int t = 0; t < RPL; ++t) y1[t][0] = acc[t][0];
-#pragma unroll
-      for (int s = 0; s < RPL; ++s) {
-        const double* lb[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) lb[t] = LT + Ly::blk(t >= s ? t : s, s) * WAVE * WAVE;
-        if (rich) {
-          double a7[D1];
-#pragma unroll
-          for (int c = 0; c < D1; ++c) a7[c] = 0.0;
-          gl_chain<D1, RPL>(a7, acc, lb, nr, s, RPL - 1);
-          wv[s] = a7[0];
-#pragma unroll
-          for (int a = 0; a < D; ++a) pv[s][a] = a7[1 + a];
-        } else {
-          double a1[1] = {0.0};
-          gl_chain<1, RPL>(a1, y1, lb, nr, s, RPL - 1);
-          wv[s] = a1[0];
-        }
-      }
-#else
-#ifdef MRBO_K1_STREAM
-      if (!rich) {
-        double y1[RPL];
-#pragma unroll
-        for (int t = 0; t < RPL; ++t) y1[t] = acc[t][0];
-        gl_k1_stream<RPL, false>(wv, y1, LT, N);
-      } else
-#endif
 #pragma unroll
       for (int s = 0; s < RPL; ++s) {
         if (rich) {
@@ -1442,7 +1089,6 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
           wv[s] = a1[0];
         }
       }
-#endif
     }
     // fantasy part: + Σ_r E[r][i] Yf[r]
 #pragma unroll
@@ -1488,7 +1134,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) nv[s][a] = x[a] - W.x0(kp, s, a);
+      for (int a = 0; a < D; ++a) nv[s][a] = x[a] - W.X0[s][a];
       const double coef = W.rowv(kp, s) ? (e.gmu * lr.cb[s] - gsig_over * lr.w[s]) : 0.0;
       ca[s] = coef * W.G12[3 * (lane + WAVE * s) + 1];
       tb[s] = coef * W.G12[3 * (lane + WAVE * s)];
@@ -1511,7 +1157,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       return s_;
     };
     constexpr int HTAIL = (Ly::NH + 1) % 16;
-    constexpr int HFULL = (HTAIL > 0 && HTAIL <= 8 && !MRBO_HESS16) ? (Ly::NH + 1) / 16 : Ly::NHC;
+    constexpr int HFULL = (HTAIL > 0 && HTAIL <= 8) ? (Ly::NH + 1) / 16 : Ly::NHC;
 #pragma unroll
     for (int ch = 0; ch < HFULL; ++ch) {
       double vv[16];
@@ -1672,9 +1318,7 @@ __device__ __forceinline__ bool chol_packed(double (&A)[D * (D + 1) / 2], double
 #pragma unroll
     for (int k = 0; k < j; ++k) s -= A[TRI(j, k)] * A[TRI(j, k)];
     ok = ok && (s > 0.0);
-#ifndef MRBO_NO_CHOL_EXIT
     if (!ok) return false;
-#endif
     double ljj;
     sqrt_rsqrt(s, ljj, idg[j]);
     A[TRI(j, j)] = ljj;
@@ -1822,9 +1466,7 @@ __device__ __forceinline__ bool newton_direction(WaveCtx<D, RPL, HW>& W, const K
   // hold different sets, so the mask stays per lane there); written by the trajectory's lane 0
   int fm = (int)W.U[Ly::U_SC + SC_FREE];
   if constexpr (HW == 1) fm = __builtin_amdgcn_readfirstlane(fm);
-#ifndef MRBO_NO_ALLFREE
   if (__builtin_amdgcn_ballot_w64(fm != (1 << D) - 1) == 0ull) return newton_direction_fm<D, RPL, HW, true>(W, kp, fm);
-#endif
   return newton_direction_fm<D, RPL, HW, false>(W, kp, fm);
 }
 
@@ -1918,7 +1560,7 @@ __device__ __forceinline__ bool tight_certified(WaveCtx<D, RPL, HW>& W, const KP
   for (int s = 0; s < RPL; ++s) {
     double rho2 = 0.0;
 #pragma unroll
-    for (int a = 0; a < D; ++a) { const double r = x[a] - W.x0(kp, s, a); rho2 = fma(r, r, rho2); }
+    for (int a = 0; a < D; ++a) { const double r = x[a] - W.X0[s][a]; rho2 = fma(r, r, rho2); }
     double psi, g1, g2;
     if constexpr (ROWS_KEPT) g1 = W.G12[3 * (lane + WAVE * s)];
     else rad_eval(W.rad, rho2, psi, g1, g2);
@@ -1953,11 +1595,6 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   double* U = W.U;
   const int lane = W.ln();
   enum { P_VAL = 0, P_TRIAL = 1, P_GRAD = 2, P_HESS = 3 };
-#ifdef MRBO_NO_FUSE_BACK
-  constexpr bool FUSE_BACK = false;
-#else
-  constexpr bool FUSE_BACK = true;   // GRAD + BACK in one evaluation call (evaluate back_after)
-#endif
   if (lane < D) {
     const double xa = clampd(W.XS[(long long)k * D + lane], U[Ly::U_LB + lane], U[Ly::U_UB + lane]);
     U[Ly::U_NX + lane] = xa;
@@ -1977,11 +1614,12 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   int phase = have_f0 ? P_GRAD : P_VAL, mode = have_f0 ? (Ly::SQ ? EV_GSTART : EV_GRAD) : EV_VALUE, it = 0, ls = 0;
   double f = have_f0 ? f0 : 0.0, ft = 0.0, t = 1.0, dec = 0.0;
   for (;;) {
-    const int back = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, FUSE_BACK && phase == P_GRAD);
+    // P_GRAD: GRAD + BACK in one evaluation call (evaluate back_after)
+    const int back = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, phase == P_GRAD);
     if (mode == EV_VALUE) ++nevals.value;
     else if (mode == EV_GRADC || mode == EV_GRAD || mode == EV_GSTART) ++nevals.grad;
     else ++nevals.hess;
-    if (FUSE_BACK && phase == P_GRAD) {   // the projected-gradient test ran inside the evaluation
+    if (phase == P_GRAD) {   // the projected-gradient test ran inside the evaluation
       if (!back) break;                   // stationary
       ++nevals.hess;                      // the BACK part (Hα) ran in the same call
       phase = P_HESS;
@@ -1997,15 +1635,6 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
       STAMP(W, 14);
       phase = P_TRIAL;
       mode = EV_VALUE;
-      continue;
-    }
-    if (phase == P_GRAD) {                 // ∇α at x ready
-      if (lane < D) U[Ly::U_NG + lane] = -U[Ly::U_GAL + lane];
-      wave_sync();
-      if (!newton_pg_ok<D, RPL, HW>(W, kp)) break;     // stationary
-      STAMP(W, 21);
-      phase = P_HESS;
-      mode = EV_BACK;
       continue;
     }
     // a VALUE evaluation: the start point (P_VAL) or a line-search trial (P_TRIAL)
@@ -2153,15 +1782,11 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
   const double* U = W.U;
   const int lane = W.ln();
   const int ns = kp.nstarts, nf = S + 1;
-#ifndef MRBO_NO_BATCH_SPLIT
   // ns ≤ 32: both half-waves take every start (lane k and k + 32); the lower half sums the
   // even data rows, the upper half the odd ones, one permlane32 swap per value adds the halves,
   // and each half evaluates every other fantasy radial function.  Both halves then hold the
   // same per-start values; the ballots below read the lower half.
   const bool split = HW == 1 && ns <= 32;   // half-wave mode: each half takes every start itself
-#else
-  const bool split = false;
-#endif
   const int kl = split ? (lane & 31) : lane;
   const int hf = split ? (lane >> 5) : 0;
   const bool act = lane < ns;
@@ -2451,7 +2076,7 @@ __device__ __forceinline__ void adjoint_pair(WaveCtx<D, RPL, HW>& W, const KPara
   for (int s = 0; s < RPL; ++s) {
     double r[D], rho2 = 0.0;
 #pragma unroll
-    for (int a = 0; a < D; ++a) { r[a] = Xq[a] - W.x0(kp, s, a); rho2 = fma(r[a], r[a], rho2); }
+    for (int a = 0; a < D; ++a) { r[a] = Xq[a] - W.X0[s][a]; rho2 = fma(r[a], r[a], rho2); }
     double psi, g1, g2;
     rad_eval(W.rad, rho2, psi, g1, g2);
 #pragma unroll
@@ -2687,9 +2312,7 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
         if (lane < D) U[Ly::U_X + lane] = kp.replay[(long long)lane + D * ((k - 1) + (long long)h * (m + (long long)M * r))];
         wave_sync();
       } else {
-#ifndef MRBO_EXP_NO_NEWTON
         st |= multistart<D, RPL, HW>(W, kp, S, nevals, lr, bsolve ? (int)tr : 0, bsolve ? (int)tr + 1 : kp.nstarts);
-#endif
         if (bsolve) {   // the start's minimizer and minimum were written by multistart
           if (lane == 0) kp.status[tr] = st & ~8;   // a NaN minimizer is the host's filter, not an error
           if (kp.evals && lane == 0) {
@@ -2757,7 +2380,6 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
   if (kp.ghq_w) value *= kp.ghq_w[(long long)m + (long long)M * t] * 0.5641895835477563;
   double gth = 0.0;
   bool grad_zero = true;
-#ifndef MRBO_EXP_NO_ADJOINT
   if (kp.with_gradient && kp.fmini > bo) {
     if (t == 0) {
       grad_zero = false;  // ∇x = -∇y₀ (Q10)
@@ -2830,7 +2452,6 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
       }
     }
   }
-#endif
   // outputs: ∇x = -(∇μ(x0)·ȳ0 + ACC[0]),  ∇θ = -Σ mixed·x̄
   wave_sync();
   const long long base = oidx;
@@ -2891,8 +2512,8 @@ __device__ __forceinline__ void wave_setup(WaveCtx<D, RPL, HW>& W, const KParams
   else W.E = kp.work + slot * kp.work_stride;
   W.C = W.E + (long long)FMAX * Ly::NRL;
   W.SUMS = W.E + (long long)(2 * FMAX + 1) * Ly::NR;   // packed layouts only (work_stride covers it)
-  if constexpr (Ly::SQ) W.STASH = W.G12 + Ly::G12 + Ly::EC;   // SQ_EAGER: wave LDS
-  else W.STASH = W.SUMS + 64 * 8;                              // GL layouts (work_stride covers it)
+  if constexpr (Ly::SQ) W.STASH = W.G12 + Ly::G12 + Ly::EC;   // see WaveCtx::STASH: never dereferenced
+  else W.STASH = W.SUMS + 64 * 8;
   W.N = kp.N;
   W.Npad = kp.Npad;
   W.rad.kind = kp.kernel;
@@ -2904,13 +2525,11 @@ __device__ __forceinline__ void wave_setup(WaveCtx<D, RPL, HW>& W, const KParams
     W.valid[s] = i < kp.N;
 #pragma unroll
     for (int a = 0; a < D; ++a) W.X0[s][a] = kp.X0[(long long)a * Ly::NR + i];
-#ifndef MRBO_NO_PAD_FAR
     // padded rows far from every point (see WaveCtx::rowv): |x − X_i|² ≈ d·1e200 stays finite, and
     // ψ, g1 = ψ'/ρ, g2 underflow to exactly 0 for the Matérn and SE kernels
     if (!W.valid[s] && kp.kernel != KERNEL_PERIODIC)
 #pragma unroll
       for (int a = 0; a < D; ++a) W.X0[s][a] = PAD_FAR;
-#endif
   }
   // zero this wave's LDS so that padded rows read as zeros
   for (int q = W.lane; q < Ly::WAVE_LDS; q += Ly::LANES) wbase[q] = 0.0;
@@ -3002,7 +2621,6 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
   int n_taken = 0;
 #endif
-#ifndef MRBO_QUEUE_SINGLE
   // One queue per XCD over a contiguous eighth of the trajectories (chunk x = [x·T/8, (x+1)·T/8),
   // its head at kp.queue[16·x], one 64-B line each): the waves of an XCD first drain the chunk of
   // their own XCD (HW_REG_XCC_ID), then the others in turn.  Consecutive trajectories then finish
@@ -3013,12 +2631,8 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   int xcc = 0, visited = 0;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
   int chunk = xcc & 7;
-#endif
   for (;;) {
     long long tr = 0;
-#ifdef MRBO_QUEUE_SINGLE
-    if (W.lane == 0) tr = atomicAdd(kp.queue, 1);
-#else
     if (W.lane == 0) {
       for (;;) {
         const long long lo = (long long)chunk * kp.T / 8, hi = (long long)(chunk + 1) * kp.T / 8;
@@ -3028,7 +2642,6 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
         chunk = (chunk + 1) & 7;
       }
     }
-#endif
     tr = __shfl(tr, 32 * W.half, WAVE);   // HW = 2: each half took its own trajectory
     if (tr >= kp.T) break;
     if (kp.order) {   // caller's schedule (a permutation; an out-of-range entry falls back to tr)
