@@ -144,6 +144,35 @@ int mrbo_device_count(void);
 int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t device, mrbo_plan_t** out);
 int mrbo_plan_destroy(mrbo_plan_t* plan);
 
+/* Surrogate batch: ONE plan, and one kernel launch per call, for S independent base surrogates
+ * s[0..S-1] (no reference counterpart: the reference runs the trials of an experiment, or the
+ * lengthscale hypotheses on one data set, one after another).  The surrogates share d, N, kernel
+ * and sigma_n2 -- a mismatch, S < 1 or an entry without X / L / c / y is MRBO_ERR_ARG, checked
+ * before any HIP call -- and differ in X, L, c, y, lengthscale, period and fmini; the plan holds,
+ * per surrogate, everything mrbo_plan_create derives from them.  p is shared: the box, rule, θ,
+ * solver options, cost model, and p->R = the restarts PER SURROGATE; so are the rnstream / nodes
+ * and the xstarts of the calls.  Every workgroup of a launch serves one surrogate (grid
+ * (⌈workgroups/S⌉, S), one set of per-XCD work queues per surrogate) and runs the code of a plain
+ * plan on it: surrogate q's block of every output is bit-identical to what mrbo_plan_create(&s[q],
+ * p) computes from the same inputs (tests/test_gpu_surrogate_batch.py).
+ *   Layout: the surrogate index is the slowest one everywhere -- x0s d×R×S; values, status,
+ *   grad_theta M×R×S; grad_x d×M×R×S; policy_x d×(h+1)×M×R×S; obs (h+1)×M×R×S; evals
+ *   MRBO_NCOUNTERS×M×R×S; dual_y_dx, replay_x d×h×M×R×S.
+ *   mrbo_simulate_mc / mrbo_simulate_ghq: one rollout launch for all S surrogates, one entry of
+ *   the timing ring (mrbo_kernel_times) per call.
+ *   mrbo_eto_reduce, mrbo_partial_moments, mrbo_merge_moments, mrbo_sga_step, mrbo_adam_step,
+ *   mrbo_stochastic_solve: the plan simply has R·S restarts -- ETO rows in (surrogate, restart)
+ *   order, active int32[R·S], x0s / m / v d×(R·S).
+ *   mrbo_base_solve: the n starts on each of the S base surrogates -- xmin d×n×S, fmin and status
+ *   n×S, evals MRBO_NCOUNTERS×n×S.   mrbo_eval_base: the P points on each surrogate -- out
+ *   (3+4d+d²)×P×S.
+ *   Work orders are per plain plan: on S > 1 mrbo_plan_set_order and
+ *   mrbo_plan_order_longest_first return MRBO_ERR_UNSUPPORTED, and mrbo_stochastic_solve keeps
+ *   the index order instead of its automatic longest-first one.
+ * mrbo_plan_create(s, p, ...) is mrbo_plan_create_batch(s, 1, p, ...).                          */
+int mrbo_plan_create_batch(const mrbo_surrogate_t* s, int32_t S, const mrbo_params_t* p, int32_t device,
+                           mrbo_plan_t** out);
+
 /* simulate_trajectory_mc for the R×M trajectories of the plan.
  *   x0s        d×R          start of each restart (tp.x0 / set_start!, rollout.jl:287)
  *   rnstream   M×(d+1)×(h+1) tp.rnstream_sequence (trajectory.jl:52-68), shared by restarts
@@ -315,7 +344,9 @@ double mrbo_last_gp_fit_ms(void);
 /* Launch geometry of a plan (no reference counterpart; measurement and FLOP accounting):
  * info[0..6] = rows per lane (1/2/4), workgroups, waves per workgroup, batched start values
  * (0/1), compile-time specialised kernel (0 generic, 1 Matérn-5/2 + EI, 2 its half-wave form: N ≤ 32, d ≤ 4, h ≤ 3, 3 Matérn-5/2 + EI + quadratic cost), LDS bytes per workgroup,
- * fantasy capacity of the kernel unit (4: the FMAX = 4 units of h ≤ 3, d ≤ 8; else 6).  Writes min(n, 7). */
+ * fantasy capacity of the kernel unit (4: the FMAX = 4 units of h ≤ 3, d ≤ 8; else 6);
+ * info[7] = S, the plan's base surrogates (1: a plain plan; info[1] stays the workgroups of a plain
+ * launch, a surrogate batch launches ⌈info[1]/S⌉ × S).  Writes min(n, 8). */
 int mrbo_plan_info(const mrbo_plan_t* plan, int32_t* info, int32_t n);
 
 /* Work order of the plan's later mrbo_simulate_mc / mrbo_simulate_ghq launches (no reference
@@ -323,7 +354,7 @@ int mrbo_plan_info(const mrbo_plan_t* plan, int32_t* info, int32_t n);
  * M×R int32 trajectory indices (m + M·r), a permutation, handed to the persistent waves in that
  * order -- e.g. longest first by the previous launch's work counters, which shortens the launch's
  * tail.  Caller-owned; it must stay valid while launches use it.  NULL restores the identity.
- * n != M×R: MRBO_ERR_ARG.  An entry outside [0, M×R) runs the trajectory of its own queue index
+ * n != M×R: MRBO_ERR_ARG; a surrogate batch (S > 1): MRBO_ERR_UNSUPPORTED.  An entry outside [0, M×R) runs the trajectory of its own queue index
  * (no write outside the outputs); tests/test_gpu_schedule.py holds every output bit-identical
  * under permuted, out-of-range and longest-first orders.  The library does not check that the
  * order is a permutation: with a duplicated index (or a mix of out-of-range entries and valid

@@ -50,6 +50,7 @@ int fail(int code, const char* fmt, ...) {
 struct mrbo_plan {
   int device = 0;
   int d = 0, N = 0, RPL = 1, NR = 64, Npad = 64;
+  int S = 1;                // base surrogates (mrbo_plan_create_batch); the scalars below: surrogate 0
   mrbo_params_t p{};
   std::vector<double> lbs, ubs, cost_w;
   int kernel = 0;
@@ -67,8 +68,9 @@ struct mrbo_plan {
   double* dytab = nullptr;  // batched starts: the launch's Y0(x_start) table (square layout, ytab_kernel)
   double* dkxb = nullptr;   // batched starts, packed layouts: global start tables (start_tables_kernel)
   double* dgtab = nullptr;
+  SurTab* dstab = nullptr;  // S > 1: the per-surrogate table (KParams::stab); dX0 ... dgtab hold S blocks
   long long work_stride = 0;
-  int* dqueue = nullptr;    // work-queue heads: one per XCD, 64 B apart (rollout_kernel)
+  int* dqueue = nullptr;    // work-queue heads: one per XCD, 64 B apart (rollout_kernel), S sets
   const int32_t* order = nullptr;   // mrbo_plan_set_order: caller-owned device permutation of M×R
                                     // (or the plan's own, mrbo_plan_order_longest_first)
   void* oorder = nullptr;           // mrbo_plan_order_longest_first: keys, ranking, sort scratch, order
@@ -407,6 +409,8 @@ static void fill_common(const mrbo_plan_t* P, KParams& kp) {
   kp.cost = P->p.cost;
   kp.cost_c0 = P->p.cost_c0;
   kp.cost_tab = P->dcost;
+  kp.stab = P->dstab;
+  kp.S = P->S;
 }
 
 // Device buffers of plan-less calls (mrbo_gp_fit: staging and the tile kernel's workspace) are
@@ -546,7 +550,7 @@ static int reduce_common(mrbo_plan_t* P, const double* values, const double* gra
                          int M, double* out, int mode, uint32_t flags, void* stream) {
   if (!P || !values || !out) return fail(MRBO_ERR_ARG, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  const int d = P->d, R = P->p.R, Ms = P->p.M;
+  const int d = P->d, R = P->p.R * P->S, Ms = P->p.M;   // a surrogate batch: R·S restarts, (surrogate, restart) order
   const size_t T = (size_t)Ms * R, W = 2 + 2 * d + 2;
   Stage sg(P);
   const double *dv = values, *dg = grad_x, *dt = grad_theta;
@@ -578,10 +582,25 @@ int mrbo_device_count(void) {
 }
 
 int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t device, mrbo_plan_t** out) {
-  if (!s || !p || !out) return fail(MRBO_ERR_ARG, "null argument");
+  return mrbo_plan_create_batch(s, 1, p, device, out);
+}
+
+int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_params_t* p, int32_t device,
+                           mrbo_plan_t** out) {
+  if (!sv || !p || !out) return fail(MRBO_ERR_ARG, "null argument");
   *out = nullptr;
+  if (S < 1) return fail(MRBO_ERR_ARG, "S=%d: at least one surrogate", (int)S);
+  const mrbo_surrogate_t* s = sv;   // surrogate 0: the shape every entry shares
   const int d = s->d, N = s->N;
-  if (d < 1 || N < 1 || !s->X || !s->L || !s->c || !s->y) return fail(MRBO_ERR_ARG, "bad surrogate (d=%d N=%d)", d, N);
+  for (int q = 0; q < S; ++q) {
+    const mrbo_surrogate_t& t = sv[q];
+    if (t.d < 1 || t.N < 1 || !t.X || !t.L || !t.c || !t.y)
+      return fail(MRBO_ERR_ARG, "bad surrogate %d (d=%d N=%d)", q, t.d, t.N);
+    if (t.d != d || t.N != N || t.kernel != s->kernel || !(t.sigma_n2 == s->sigma_n2))
+      return fail(MRBO_ERR_ARG, "surrogate %d differs from surrogate 0 in d, N, kernel or sigma_n2 "
+                  "(d %d/%d, N %d/%d, kernel %d/%d, sigma_n2 %g/%g)", q, t.d, d, t.N, N, t.kernel, s->kernel,
+                  t.sigma_n2, s->sigma_n2);
+  }
   if (d > 16) return fail(MRBO_ERR_UNSUPPORTED, "d=%d > 16 not compiled", d);
   if (N > 512) return fail(MRBO_ERR_UNSUPPORTED, "N=%d > 512 not compiled", N);
   if (d > 8 && N > 128) return fail(MRBO_ERR_UNSUPPORTED, "d=%d > 8 with N=%d > 128 not compiled", d, N);
@@ -604,11 +623,13 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
       if (!(p->ubs[a] > p->lbs[a])) return fail(MRBO_ERR_ARG, "cost model needs ub > lb (dimension %d)", a);
     }
   }
-  if (s->kernel == MRBO_KERNEL_PERIODIC && !(s->period > 0.0)) return fail(MRBO_ERR_ARG, "period %g", s->period);
-  const int ldL = s->ldL > 0 ? s->ldL : N;
+  for (int q = 0; q < S; ++q)
+    if (s->kernel == MRBO_KERNEL_PERIODIC && !(sv[q].period > 0.0)) return fail(MRBO_ERR_ARG, "period %g", sv[q].period);
+  if ((long long)p->R * S > 0x7FFFFFFFll) return fail(MRBO_ERR_ARG, "R*S = %lld restarts", (long long)p->R * S);
 
   mrbo_plan* P = new mrbo_plan();
   P->device = device;
+  P->S = S;
   P->d = d;
   P->N = N;
   P->RPL = (N <= 64) ? 1 : (N <= 128) ? 2 : (N <= 256) ? 4 : 8;
@@ -624,44 +645,67 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
   P->kernel = s->kernel;
   P->ell = s->lengthscale;
   P->sn2 = s->sigma_n2;
-  P->fmini = s->fmini;
-  P->fmin_base = s->y[0];
-  for (int i = 1; i < N; ++i) P->fmin_base = std::min(P->fmin_base, s->y[i]);
-  const double ell = s->lengthscale;
-  switch (s->kernel) {
-    case 0: P->cK = std::sqrt(5.0) / ell; P->d2psi0 = -P->cK * P->cK / 3.0; break;
-    case 1: P->cK = std::sqrt(3.0) / ell; P->d2psi0 = -P->cK * P->cK; break;
-    case 2: P->cK = 1.0 / ell; P->d2psi0 = P->cK * P->cK; break;
-    case 4: P->cK = 1.0 / (ell * ell); P->cP = 2.0 * M_PI / s->period; P->d2psi0 = -P->cK * P->cP * P->cP; break;
-    default: P->cK = 1.0 / (ell * ell); P->d2psi0 = -P->cK; break;
-  }
-  P->psi0 = 1.0;
-  // max_ρ |ψ'(ρ)| in closed form (+1% margin) and √(ψ(0)·(−ψ''(0))) for the gradient certificate
-  switch (P->kernel) {
-    case 0: { const double s = 0.5 * (1.0 + std::sqrt(5.0));
-              P->gcert_mu = 1.01 * P->cK * (s / 3.0) * (1.0 + s) * std::exp(-s); break; }
-    case 1: P->gcert_mu = 1.01 * P->cK * std::exp(-1.0); break;
-    case 2: P->gcert_mu = 1.01 * P->cK; break;
-    case 4: P->gcert_mu = 1.01 * P->cK * P->cP; break;   // |ψ'| = ψ (2π/(pℓ²)) |sin t| ≤ 2π/(pℓ²)
-    default: P->gcert_mu = 1.01 * std::sqrt(P->cK) * std::exp(-0.5); break;
-  }
-  P->gcert_sig = (P->d2psi0 < 0.0) ? 1.01 * std::sqrt(P->psi0 * -P->d2psi0) : -1.0;
-
-  // L0^-1 by forward substitution on the unit columns, packed column-major (Npad rows)
-  const int Npad = P->Npad;
-  std::vector<double> Li((size_t)N * N, 0.0);  // col-major N×N
-  for (int j = 0; j < N; ++j) {
-    double* col = &Li[(size_t)j * N];
-    for (int i = j; i < N; ++i) {
-      double sacc = (i == j) ? 1.0 : 0.0;
-      for (int k = j; k < i; ++k) sacc -= s->L[i + (size_t)ldL * k] * col[k];
-      col[i] = sacc / s->L[i + (size_t)ldL * i];
+  // what one surrogate alone determines: the kernel-function constants, the closed-form bounds of
+  // the gradient certificate, min y (surrogate 0 in the plan's own fields, all S in the table)
+  std::vector<SurTab> tabs((size_t)S);
+  for (int q = 0; q < S; ++q) {
+    const mrbo_surrogate_t& t = sv[q];
+    SurTab& e = tabs[q];
+    memset(&e, 0, sizeof e);
+    e.fmini = t.fmini;
+    e.fmin_base = t.y[0];
+    for (int i = 1; i < N; ++i) e.fmin_base = std::min(e.fmin_base, t.y[i]);
+    const double ell = t.lengthscale;
+    e.ell = ell;
+    switch (t.kernel) {
+      case 0: e.cK = std::sqrt(5.0) / ell; e.d2psi0 = -e.cK * e.cK / 3.0; break;
+      case 1: e.cK = std::sqrt(3.0) / ell; e.d2psi0 = -e.cK * e.cK; break;
+      case 2: e.cK = 1.0 / ell; e.d2psi0 = e.cK * e.cK; break;
+      case 4: e.cK = 1.0 / (ell * ell); e.cP = 2.0 * M_PI / t.period; e.d2psi0 = -e.cK * e.cP * e.cP; break;
+      default: e.cK = 1.0 / (ell * ell); e.d2psi0 = -e.cK; break;
     }
+    // max_ρ |ψ'(ρ)| in closed form (+1% margin) and √(ψ(0)·(−ψ''(0))) for the gradient certificate
+    switch (t.kernel) {
+      case 0: { const double s5 = 0.5 * (1.0 + std::sqrt(5.0));
+                e.gcert_mu = 1.01 * e.cK * (s5 / 3.0) * (1.0 + s5) * std::exp(-s5); break; }
+      case 1: e.gcert_mu = 1.01 * e.cK * std::exp(-1.0); break;
+      case 2: e.gcert_mu = 1.01 * e.cK; break;
+      case 4: e.gcert_mu = 1.01 * e.cK * e.cP; break;   // |ψ'| = ψ (2π/(pℓ²)) |sin t| ≤ 2π/(pℓ²)
+      default: e.gcert_mu = 1.01 * std::sqrt(e.cK) * std::exp(-0.5); break;
+    }
+    e.gcert_sig = (e.d2psi0 < 0.0) ? 1.01 * std::sqrt(1.0 * -e.d2psi0) : -1.0;
+    e.gcert_d2 = (e.d2psi0 < 0.0) ? 1.01 * std::sqrt(-e.d2psi0) : -1.0;
   }
-  std::vector<double> X0((size_t)d * P->NR, 0.0), c0(P->NR, 0.0);
-  for (int i = 0; i < N; ++i) {
-    for (int a = 0; a < d; ++a) X0[(size_t)a * P->NR + i] = s->X[a + (size_t)d * i];
-    c0[i] = s->c[i];
+  P->fmini = tabs[0].fmini;
+  P->fmin_base = tabs[0].fmin_base;
+  P->cK = tabs[0].cK; P->cP = tabs[0].cP; P->d2psi0 = tabs[0].d2psi0;
+  P->psi0 = 1.0;
+  P->gcert_mu = tabs[0].gcert_mu;
+  P->gcert_sig = tabs[0].gcert_sig;
+
+  // L0^-1 of every surrogate by forward substitution on the unit columns (col-major N×N)
+  const int Npad = P->Npad;
+  (void)Npad;
+  std::vector<std::vector<double>> Lis((size_t)S);
+  std::vector<double> X0((size_t)S * d * P->NR, 0.0), c0((size_t)S * P->NR, 0.0);
+  for (int q = 0; q < S; ++q) {
+    const mrbo_surrogate_t& t = sv[q];
+    const int ldL = t.ldL > 0 ? t.ldL : N;
+    std::vector<double>& Li = Lis[q];
+    Li.assign((size_t)N * N, 0.0);
+    for (int j = 0; j < N; ++j) {
+      double* col = &Li[(size_t)j * N];
+      for (int i = j; i < N; ++i) {
+        double sacc = (i == j) ? 1.0 : 0.0;
+        for (int k = j; k < i; ++k) sacc -= t.L[i + (size_t)ldL * k] * col[k];
+        col[i] = sacc / t.L[i + (size_t)ldL * i];
+      }
+    }
+    double* X0q = &X0[(size_t)q * d * P->NR];
+    for (int i = 0; i < N; ++i) {
+      for (int a = 0; a < d; ++a) X0q[(size_t)a * P->NR + i] = t.X[a + (size_t)d * i];
+      c0[(size_t)q * P->NR + i] = t.c[i];
+    }
   }
 
   hipError_t e = hipSetDevice(device);
@@ -680,8 +724,11 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
   }
   // the kernel's image of L0⁻¹ (zero above the diagonal and on padded rows); the global
   // variant appends a row-packed copy (row k: columns 0..k) for the backward product
-  std::vector<double> packed((size_t)ks.linv_dev, 0.0);
-  for (int j = 0; j < N; ++j)
+  std::vector<double> packed_all((size_t)ks.linv_dev * S, 0.0);
+  for (int q = 0; q < S; ++q) {
+   double* packed = &packed_all[(size_t)ks.linv_dev * q];
+   const std::vector<double>& Li = Lis[q];
+   for (int j = 0; j < N; ++j)
     for (int i = j; i < N; ++i) {
       const size_t blk = (size_t)(i / 64) * (i / 64 + 1) / 2 + j / 64;   // block (i/64, j/64), j/64 ≤ i/64
       size_t at;
@@ -703,6 +750,7 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
           packed[2 * nblk * 64 * 64 + (size_t)slot * 64 * 65 + (size_t)(j % 64) * 65 + i % 64] = Li[i + (size_t)N * j];
       }
     }
+  }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete P; return fail(MRBO_ERR_HIP, "device props"); }
   const size_t linv_bytes = sizeof(double) * (size_t)ks.linv_doubles;
@@ -743,7 +791,7 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
     int wpg1 = 0, blocks1 = 0;
     size_t smem1 = 0;
     const int waves1 = pick_grid(rk, fixed + kxb_bytes, wave_bytes, prop.multiProcessorCount, wpg1, blocks1,
-                                 smem1);
+                                 smem1, 0, maxw);
     if (waves1 >= waves0 && waves1 > 0) { P->batch = 1; P->wpg = wpg1; P->blocks = blocks1; P->smem = smem1; }
   }
   if (!P->batch) { P->wpg = wpg0; P->blocks = blocks0; P->smem = smem0; }
@@ -755,22 +803,26 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
     delete P;
     return fail(MRBO_ERR_UNSUPPORTED, "no feasible launch configuration");
   }
-  const int slots = std::max(P->blocks * P->wpg, P->eblocks * P->ewpg);
+  // a surrogate batch launches grids (⌈blocks/S⌉, S): its wave slots can exceed the plain grid's
+  const int slots = std::max({P->blocks * P->wpg, P->eblocks * P->ewpg,
+                              std::max(1, (P->blocks + S - 1) / S) * S * P->wpg,
+                              std::max(1, (P->eblocks + S - 1) / S) * S * P->ewpg});
   // per wave slot: E (FMAX × NR) and C ((FMAX+1) × NR), then the batched start pass's per-start
   // sums (64 × 8) for the packed layouts
   P->work_stride = (long long)(2 * FMAX + 1) * P->NR + 64 * 8;
   bool ok = hipMalloc(&P->dX0, sizeof(double) * X0.size()) == hipSuccess &&
             hipMalloc(&P->dc0, sizeof(double) * c0.size()) == hipSuccess &&
-            hipMalloc(&P->dLinv, sizeof(double) * packed.size()) == hipSuccess &&
+            hipMalloc(&P->dLinv, sizeof(double) * packed_all.size()) == hipSuccess &&
             hipMalloc(&P->dlbs, sizeof(double) * d) == hipSuccess &&
             hipMalloc(&P->dubs, sizeof(double) * d) == hipSuccess &&
             hipMalloc(&P->dwork, sizeof(double) * (size_t)slots * P->work_stride) == hipSuccess &&
             (!P->batch || !ks.square ||
-             hipMalloc(&P->dytab, sizeof(double) * (size_t)ns * P->NR) == hipSuccess) &&
+             hipMalloc(&P->dytab, sizeof(double) * (size_t)ns * P->NR * S) == hipSuccess) &&
             (!P->batch || ks.square ||
-             (hipMalloc(&P->dkxb, sizeof(double) * (size_t)P->NR * ns) == hipSuccess &&
-              hipMalloc(&P->dgtab, sizeof(double) * (size_t)ns * ng) == hipSuccess)) &&
-            hipMalloc(&P->dqueue, sizeof(int) * MRBO_QUEUE_INTS) == hipSuccess &&
+             (hipMalloc(&P->dkxb, sizeof(double) * (size_t)P->NR * ns * S) == hipSuccess &&
+              hipMalloc(&P->dgtab, sizeof(double) * (size_t)ns * ng * S) == hipSuccess)) &&
+            hipMalloc(&P->dqueue, sizeof(int) * MRBO_QUEUE_INTS * S) == hipSuccess &&
+            (S == 1 || hipMalloc(&P->dstab, sizeof(SurTab) * S) == hipSuccess) &&
             (P->p.cost == MRBO_COST_NONE || hipMalloc(&P->dcost, sizeof(double) * 3 * d) == hipSuccess);
   if (ok && P->p.cost != MRBO_COST_NONE) {
     std::vector<double> tab(3 * (size_t)d);
@@ -783,10 +835,22 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
   }
   ok = ok && hipMemcpy(P->dX0, X0.data(), sizeof(double) * X0.size(), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(P->dc0, c0.data(), sizeof(double) * c0.size(), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(P->dLinv, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(P->dLinv, packed_all.data(), sizeof(double) * packed_all.size(), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(P->dlbs, P->lbs.data(), sizeof(double) * d, hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(P->dubs, P->ubs.data(), sizeof(double) * d, hipMemcpyHostToDevice) == hipSuccess &&
        hipMemset(P->dwork, 0, sizeof(double) * (size_t)slots * P->work_stride) == hipSuccess;
+  if (ok && S > 1) {   // the per-surrogate table: block q of every image and start table
+    for (int q = 0; q < S; ++q) {
+      SurTab& e = tabs[q];
+      e.X0 = P->dX0 + (size_t)q * d * P->NR;
+      e.c0 = P->dc0 + (size_t)q * P->NR;
+      e.Linv = P->dLinv + (size_t)q * ks.linv_dev;
+      e.ytab = P->dytab ? P->dytab + (size_t)q * ns * P->NR : nullptr;
+      e.kxb_g = P->dkxb ? P->dkxb + (size_t)q * P->NR * ns : nullptr;
+      e.gtab_g = P->dgtab ? P->dgtab + (size_t)q * ns * ng : nullptr;
+    }
+    ok = hipMemcpy(P->dstab, tabs.data(), sizeof(SurTab) * S, hipMemcpyHostToDevice) == hipSuccess;
+  }
   // the timing ring's events are created on first use by a launch (launch_events), not here: a plan
   // used for a few launches (the Julia drop-in's R = 1 calls) creates only what it records
   if (!ok) {
@@ -800,7 +864,7 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
 int mrbo_plan_destroy(mrbo_plan_t* P) {
   if (!P) return MRBO_OK;
   for (void* b : {(void*)P->dX0, (void*)P->dc0, (void*)P->dLinv, (void*)P->dlbs, (void*)P->dubs, (void*)P->dwork, (void*)P->dytab,
-                  (void*)P->dkxb, (void*)P->dgtab, (void*)P->dqueue, (void*)P->dcost, P->oorder})
+                  (void*)P->dkxb, (void*)P->dgtab, (void*)P->dqueue, (void*)P->dcost, (void*)P->dstab, P->oorder})
     if (b) (void)hipFree(b);
   for (auto& b : P->stage)
     if (b.first) (void)hipFree(b.first);
@@ -828,12 +892,12 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
   if (with_grad && (!grad_x || !grad_theta)) return fail(MRBO_ERR_ARG, "gradient containers required");
   hipStream_t st = (hipStream_t)stream;
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
-  const int d = P->d, h = P->p.h, M = P->p.M, R = P->p.R;
-  const size_t T = (size_t)M * R;
+  const int d = P->d, h = P->p.h, M = P->p.M, R = P->p.R * P->S, S = P->S;
+  const size_t T = (size_t)M * R;   // over all S surrogates: the sizes of the staged arrays
   KParams kp;
   fill_common(P, kp);
   kp.with_gradient = with_grad ? 1 : 0;
-  kp.T = (long long)T;
+  kp.T = (long long)(T / S);        // the kernel's trajectory range: ONE surrogate's M×R
   Stage sg(P);
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
   double *dvalues = values, *dgx = grad_x, *dgt = grad_theta, *dpol = policy_x, *dobs = obs;
@@ -857,7 +921,7 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
   kp.status = (int*)dstatus; kp.policy = dpol; kp.obs = dobs; kp.evals = (long long*)devals;
   kp.order = P->order;
   kp.skip_active = P->skip_active;
-  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS, st));
+  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS * S, st));
 #ifdef MRBO_STAMPS
   static unsigned long long* dstamps = nullptr;
   if (!dstamps) HIP_TRY(hipMalloc(&dstamps, sizeof(unsigned long long) * NSTAMP_SLOTS));
@@ -895,7 +959,9 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
     HIP_TRY(hipEventCreate(&P->ev[2 * slot + 1]));
   }
   HIP_TRY(hipEventRecord(P->ev[2 * slot], st));
-  launch_rollout(d, P->RPL, P->fx, P->spec, dim3(P->blocks), dim3(P->wpg * WAVE), P->smem, st, kp);
+  // a surrogate batch: the plan's workgroups shared out over the S surrogates, grid (⌈blocks/S⌉, S)
+  launch_rollout(d, P->RPL, P->fx, P->spec, dim3(S > 1 ? std::max(1, (P->blocks + S - 1) / S) : P->blocks, S),
+                 dim3(P->wpg * WAVE), P->smem, st, kp);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(P->ev[2 * slot + 1], st));
   ++P->nlaunch;
@@ -1022,7 +1088,7 @@ int mrbo_sga_step(mrbo_plan_t* P, const double* eto, double* x0s, int32_t* activ
   if (!P || !eto || !x0s || !active) return fail(MRBO_ERR_ARG, "null argument");
   if (flags & MRBO_FLAG_HOST_POINTERS) return fail(MRBO_ERR_ARG, "mrbo_sga_step takes device pointers");
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
-  const int R = P->p.R;
+  const int R = P->p.R * P->S;
   hipLaunchKernelGGL(sga_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, eto, x0s, (int*)active, R, P->d,
                      sample_size, eta);
   HIP_TRY(hipGetLastError());
@@ -1036,7 +1102,7 @@ int mrbo_adam_step(mrbo_plan_t* P, const double* eto, double* x0s, int32_t* acti
   if (flags & MRBO_FLAG_HOST_POINTERS) return fail(MRBO_ERR_ARG, "mrbo_adam_step takes device pointers");
   if (t < 1) return fail(MRBO_ERR_ARG, "t=%d: the update count starts at 1", t);
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
-  const int R = P->p.R;
+  const int R = P->p.R * P->S;
   const double c1 = 1.0 - std::pow(beta1, (double)t), c2 = 1.0 - std::pow(beta2, (double)t);
   hipLaunchKernelGGL(adam_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, eto, x0s, (int*)active, m, v,
                      R, P->d, sample_size, eta, beta1, beta2, eps, c1, c2);
@@ -1059,7 +1125,7 @@ int mrbo_merge_moments(mrbo_plan_t* P, int32_t nshards, const double* moments, c
   }
   if (tot < 1) return fail(MRBO_ERR_ARG, "no samples in any shard");
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
-  const int R = P->p.R, d = P->d, nthr = R * (d + 2);
+  const int R = P->p.R * P->S, d = P->d, nthr = R * (d + 2);
   hipLaunchKernelGGL(merge_kernel, dim3((nthr + 63) / 64), dim3(64), 0, (hipStream_t)stream, moments, (int)nshards, cnt,
                      R, d, eto);
   HIP_TRY(hipGetLastError());
@@ -1091,7 +1157,7 @@ int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, c
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   hipStream_t st = (hipStream_t)stream;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
-  const int d = P->d, M = P->p.M, R = P->p.R, h = P->p.h, W = 2 + 2 * d + 2;
+  const int d = P->d, M = P->p.M, R = P->p.R * P->S, h = P->p.h, W = 2 + 2 * d + 2;   // R·S restarts
   const size_t T = (size_t)M * R;
   const size_t nx = (size_t)d * R, nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
   const size_t ndual = (size_t)d * std::max(h, 1) * T;
@@ -1160,7 +1226,8 @@ int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, c
     const int32_t* saved;
     ~OrderGuard() { P->order = saved; }
   } oguard{P, P->order};
-  const bool auto_order = P->order == nullptr && o->iterations > 1;
+  // (a surrogate batch keeps the identity: the longest-first order is not defined across surrogates)
+  const bool auto_order = P->order == nullptr && o->iterations > 1 && P->S == 1;
   int64_t* devals = auto_order ? (int64_t*)solve_slot(P, 13, sizeof(int64_t) * NCOUNT * T) : nullptr;
   if (auto_order && !devals) return fail(MRBO_ERR_NOMEM, "outer-ascent work counters");
   int rc = MRBO_OK;
@@ -1214,18 +1281,20 @@ int mrbo_eval_base(mrbo_plan_t* P, int32_t npts, const double* xs, double* out, 
   Stage sg(P);
   const double* dxs = xs;
   double* dout = out;
+  const int S = P->S;   // the same points on each surrogate: out holds S blocks of stride×P
   if (flags & MRBO_FLAG_HOST_POINTERS) {
-    if (sg.in(xs, (size_t)d * npts, &dxs) || sg.out(stride * npts, out, &dout))
+    if (sg.in(xs, (size_t)d * npts, &dxs) || sg.out(stride * npts * S, out, &dout))
       return fail(MRBO_ERR_NOMEM, "staging allocation failed");
   }
   kp.pts = dxs;
   kp.pts_out = dout;
-  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS, st));
-  launch_evalb(d, P->RPL, P->fx, dim3(P->eblocks), dim3(P->ewpg * WAVE), P->esmem, st, kp);
+  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS * S, st));
+  launch_evalb(d, P->RPL, P->fx, dim3(S > 1 ? std::max(1, (P->eblocks + S - 1) / S) : P->eblocks, S),
+               dim3(P->ewpg * WAVE), P->esmem, st, kp);
   HIP_TRY(hipGetLastError());
   if (flags & MRBO_FLAG_HOST_POINTERS) {
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * stride * npts, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * stride * npts * S, hipMemcpyDeviceToHost));
   }
   return MRBO_OK;
 }
@@ -1254,9 +1323,11 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   int32_t* dst = status;
   int64_t* dev = evals;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
+  const size_t S = (size_t)P->S;   // the n starts on each surrogate: every output holds S blocks
   if (host) {
-    if (sg.in(xstarts, (size_t)d * n, &dxs) || sg.out((size_t)d * n, xmin, &dx) || sg.out((size_t)n, fmin, &df) ||
-        sg.out((size_t)n, status, &dst) || sg.out((size_t)NCOUNT * n, evals, &dev))
+    if (sg.in(xstarts, (size_t)d * n, &dxs) || sg.out((size_t)d * n * S, xmin, &dx) ||
+        sg.out((size_t)n * S, fmin, &df) || sg.out((size_t)n * S, status, &dst) ||
+        sg.out((size_t)NCOUNT * n * S, evals, &dev))
       return fail(MRBO_ERR_NOMEM, "staging allocation failed");
   }
   kp.xstarts = dxs;
@@ -1264,16 +1335,17 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   kp.values = df;
   kp.status = (int*)dst;
   kp.evals = (long long*)dev;
-  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS, st));
-  const int blocks = std::min(P->blocks, (n + P->wpg - 1) / P->wpg);
-  launch_rollout(d, P->RPL, P->fx, P->spec, dim3(blocks), dim3(P->wpg * WAVE), P->smem, st, kp);
+  HIP_TRY(hipMemsetAsync(P->dqueue, 0, sizeof(int) * MRBO_QUEUE_INTS * S, st));
+  const int bx = S > 1 ? std::max(1, (P->blocks + (int)S - 1) / (int)S) : P->blocks;
+  const int blocks = std::min(bx, (n + P->wpg - 1) / P->wpg);
+  launch_rollout(d, P->RPL, P->fx, P->spec, dim3(blocks, (unsigned)S), dim3(P->wpg * WAVE), P->smem, st, kp);
   HIP_TRY(hipGetLastError());
   if (host) {
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(xmin, dx, sizeof(double) * d * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(fmin, df, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status, dst, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (evals) HIP_TRY(hipMemcpy(evals, dev, sizeof(int64_t) * NCOUNT * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(xmin, dx, sizeof(double) * d * n * S, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fmin, df, sizeof(double) * n * S, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, dst, sizeof(int32_t) * n * S, hipMemcpyDeviceToHost));
+    if (evals) HIP_TRY(hipMemcpy(evals, dev, sizeof(int64_t) * NCOUNT * n * S, hipMemcpyDeviceToHost));
   }
   return MRBO_OK;
 }
@@ -1409,6 +1481,9 @@ double mrbo_last_gp_fit_ms(void) { return g_gpfit_ms; }
 
 int mrbo_plan_set_order(mrbo_plan_t* P, const int32_t* order, int64_t n) {
   if (!P) return fail(MRBO_ERR_ARG, "null plan");
+  if (P->S > 1)
+    return fail(MRBO_ERR_UNSUPPORTED, "mrbo_plan_set_order: a work order is not supported on a surrogate batch (S=%d); "
+                "each surrogate's trajectories run in index order", P->S);
   if (order && n != (int64_t)P->p.M * P->p.R) return fail(MRBO_ERR_ARG, "order length != M*R");
   P->order = order;
   return MRBO_OK;
@@ -1416,6 +1491,9 @@ int mrbo_plan_set_order(mrbo_plan_t* P, const int32_t* order, int64_t n) {
 
 int mrbo_plan_order_longest_first(mrbo_plan_t* P, const int64_t* evals, int32_t* order_out, void* stream) {
   if (!P || !evals) return fail(MRBO_ERR_ARG, "null argument");
+  if (P->S > 1)
+    return fail(MRBO_ERR_UNSUPPORTED, "mrbo_plan_order_longest_first: the longest-first order is not supported on a "
+                "surrogate batch (S=%d)", P->S);
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   const long long T = (long long)P->p.M * P->p.R;
   if (T > 0x7FFFFFFFll) return fail(MRBO_ERR_ARG, "M*R = %lld: more than 2^31 - 1 trajectories", T);
@@ -1438,8 +1516,8 @@ int mrbo_plan_order_longest_first(mrbo_plan_t* P, const int64_t* evals, int32_t*
 
 int mrbo_plan_info(const mrbo_plan_t* P, int32_t* info, int32_t n) {
   if (!P || !info || n < 0) return fail(MRBO_ERR_ARG, "bad arguments");
-  const int32_t v[7] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6};
-  for (int i = 0; i < n && i < 7; ++i) info[i] = v[i];
+  const int32_t v[8] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6, P->S};
+  for (int i = 0; i < n && i < 8; ++i) info[i] = v[i];
   return MRBO_OK;
 }
 

@@ -54,6 +54,21 @@ __host__ __device__ constexpr int gl_lds_slot(int b) {
 //          from the launch's start tables (stage_start_tables), only surface terms are computed
 enum { EV_VALUE = 0, EV_GRAD = 1, EV_DRAW = 2, EV_FULL = 3, EV_RICH = 4, EV_BACK = 5, EV_GRADC = 6, EV_GSTART = 7 };
 
+// Surrogate batches (mrbo_plan_create_batch, S > 1): entry s of KParams::stab, the base surrogate
+// that the workgroups with blockIdx.y = s serve.  It holds what mrbo_plan_create derives from one
+// surrogate; surrogate_select() (mrbo_rollout.hip) writes it over the kernel's own copy of KParams.
+struct SurTab {
+  const double* X0;     // as KParams::X0, c0, Linv: this surrogate's device images
+  const double* c0;
+  const double* Linv;
+  double* ytab;         // this surrogate's start tables (kp.batch)
+  double* kxb_g;
+  double* gtab_g;
+  double ell, cK, cP, d2psi0;
+  double fmin_base, fmini;
+  double gcert_mu, gcert_sig, gcert_d2;
+};
+
 struct KParams {
   int d, N, Npad, h, M, R, nstarts;
   int kernel;
@@ -114,6 +129,13 @@ struct KParams {
   // xstarts) on the base surrogate (rbf_optim.jl:35-66); minimizer -> policy (d×T), minimum ->
   // values (T), no trajectory
   int base_solve;
+  // surrogate batch: S base surrogates in one launch, grid (blocks, S), each workgroup on surrogate
+  // blockIdx.y.  Null for a plain plan (S = 1).  kp.T and kp.R stay those of ONE surrogate; inputs
+  // and outputs hold S such blocks, the surrogate index slowest, addressed by the global trajectory
+  // index tr + blockIdx.y·T
+  // (a pointer to a table, not array members: see cost_tab)
+  const SurTab* stab;
+  int S;
 };
 
 

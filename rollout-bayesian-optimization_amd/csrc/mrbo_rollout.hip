@@ -2575,6 +2575,40 @@ __device__ __forceinline__ void spec_params(KParams& kp) {
   }
 }
 
+// Surrogate batch (kp.stab, grid (blocks, S)): this workgroup serves base surrogate s = blockIdx.y.
+// Its images, start tables and derived scalars replace those of the kernel's copy of KParams --
+// wave-uniform scalar loads, once per workgroup, consumed by the prologue (stage_linv,
+// stage_start_tables, wave_setup) except c0 and fmini, which every trajectory reads.  Everything
+// that is indexed by trajectory (x0s, δx, replay, every output, skip_active) stays where it is: the
+// kernels hand trajectory() the GLOBAL index tr + s·T, whose restart tr / M = r + s·R and sample
+// tr % M = m address block s of the S blocks (surrogate index slowest), so trajectory() and
+// everything below it run what a plain plan on surrogate s runs.  The work queues are one set of 8
+// heads per surrogate (surrogate_queue), the per-wave work slots of the packed layouts are counted
+// over the whole grid.  gcert_sig keeps surrogate 0's value in kp -- the code tests its sign, which
+// the kernel family alone decides -- and the per-wave LDS constant is set by surrogate_constants.
+// A plain launch (stab null, blockIdx.y = 0) takes none of this and adds zero everywhere.
+__device__ __forceinline__ void surrogate_select(KParams& kp) {
+  if (!kp.stab) return;
+  const long long s = blockIdx.y;
+  const SurTab& e = kp.stab[s];
+  kp.X0 = e.X0; kp.c0 = e.c0; kp.Linv = e.Linv;
+  kp.ytab = e.ytab; kp.kxb_g = e.kxb_g; kp.gtab_g = e.gtab_g;
+  kp.ell = e.ell; kp.cK = e.cK; kp.cP = e.cP; kp.d2psi0 = e.d2psi0;
+  kp.fmin_base = e.fmin_base; kp.fmini = e.fmini;
+  kp.gcert_mu = e.gcert_mu; kp.gcert_d2 = e.gcert_d2;
+  kp.work += s * gridDim.x * (blockDim.x / WAVE) * kp.work_stride;
+  // mrbo_base_solve: item tr + s·n of surrogate s starts from column tr of the shared starts
+  if (kp.base_solve) kp.xstarts -= s * kp.T * kp.d;
+}
+// the first queue head of this workgroup's surrogate, in ints from kp.queue
+__device__ __forceinline__ int surrogate_queue() { return (int)blockIdx.y * MRBO_QUEUE_INTS; }
+// after wave_setup, before its wave_sync: the per-wave LDS constants that wave_setup took from kp
+// and surrogate_select left at surrogate 0's value
+template <int D, int RPL, int HW>
+__device__ __forceinline__ void surrogate_constants(WaveCtx<D, RPL, HW>& W, const KParams& kp) {
+  if (kp.stab && W.lane == 0) W.U[Lay<D, RPL, HW>::U_KC + KC_GCSIG] = kp.stab[blockIdx.y].gcert_sig;
+}
+
 // stage L0⁻¹ (and the inner-solve start points) once per workgroup (the only block barrier)
 template <int D, int RPL, int HW>
 __device__ __forceinline__ void stage_linv(const KParams& kp, double* smem) {
@@ -2593,6 +2627,7 @@ template <int D, int RPL, int SPEC, int HW = 1>
 __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RPL, HW>::waves_per_simd)) ytab_kernel(KParams kp_in) {
   KParams kp = kp_in;
   spec_params<SPEC>(kp);
+  surrogate_select(kp);
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using Ly = Lay<D, RPL, HW>;
   if constexpr (Ly::SQ) {
@@ -2605,6 +2640,7 @@ template <int D, int RPL, int SPEC, int HW = 1>
 __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RPL, HW>::waves_per_simd)) rollout_kernel(KParams kp_in) {
   KParams kp = kp_in;   // a local copy: the fixed fields below propagate as constants
   spec_params<SPEC>(kp);
+  surrogate_select(kp);
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using Ly = Lay<D, RPL, HW>;
   stage_linv<D, RPL, HW>(kp, smem);
@@ -2613,6 +2649,7 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   }
   WaveCtx<D, RPL, HW> W;
   wave_setup<D, RPL, HW>(W, kp, smem, threadIdx.x / WAVE);
+  surrogate_constants<D, RPL, HW>(W, kp);
   wave_sync();
 #ifdef MRBO_STAMPS
   W.tlast = __builtin_amdgcn_s_memtime();
@@ -2636,7 +2673,7 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
     if (W.lane == 0) {
       for (;;) {
         const long long lo = (long long)chunk * kp.T / 8, hi = (long long)(chunk + 1) * kp.T / 8;
-        const long long idx = lo + atomicAdd(kp.queue + 16 * chunk, 1);
+        const long long idx = lo + atomicAdd(kp.queue + surrogate_queue() + 16 * chunk, 1);
         if (idx < hi) { tr = idx; break; }
         if (++visited == 8) { tr = kp.T; break; }
         chunk = (chunk + 1) & 7;
@@ -2648,6 +2685,7 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
       const long long id = kp.order[tr];
       tr = (id >= 0 && id < kp.T) ? id : tr;
     }
+    tr += (long long)blockIdx.y * kp.T;   // surrogate batch: the global index (block blockIdx.y of the outputs)
     if (kp.skip_active && kp.skip_active[tr / kp.M] == 0) continue;   // a stopped restart (outer ascent)
 #ifdef MRBO_TAIL
     const unsigned long long t_tr = __builtin_amdgcn_s_memrealtime();
@@ -2684,6 +2722,7 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
 // The forward product walks the packed-by-columns image of L0⁻¹ (column j: rows j..Npad-1).
 template <int D, int RPL, int HW = 1>
 __global__ void __launch_bounds__(WAVE) start_tables_kernel(KParams kp) {
+  surrogate_select(kp);   // grid (nstarts, S)
   using Ly = Lay<D, RPL, HW>;
   constexpr int NR = Ly::NR, D1 = Ly::D1;
   __shared__ double Bs[NR * D1];
@@ -2756,6 +2795,7 @@ __global__ void __launch_bounds__(WAVE) start_tables_kernel(KParams kp) {
 // eval(s, x, θ) on the base surrogate for P points (fixture / primitive parity path)
 template <int D, int RPL, int HW = 1>
 __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RPL, HW>::waves_per_simd)) eval_base_kernel(KParams kp) {
+  surrogate_select(kp);
   using Ly = Lay<D, RPL, HW>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   for (int q = threadIdx.x; q < (int)Ly::LINV_DOUBLES; q += blockDim.x) smem[q] = kp.Linv[Ly::LINV_LDS_SRC + q];
@@ -2771,10 +2811,11 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   const int stride = 3 + 4 * D + D * D;
   for (;;) {
     long long p = 0;
-    if (lane == 0) p = atomicAdd(kp.queue, 1);
+    if (lane == 0) p = atomicAdd(kp.queue + surrogate_queue(), 1);
     p = __shfl(p, 0, WAVE);
     if (p >= kp.T) break;
     if (lane < D) W.U[Ly::U_X + lane] = kp.pts[p * D + lane];
+    p += (long long)blockIdx.y * kp.T;   // surrogate batch: the shared points, this surrogate's rows
     wave_sync();
     evaluate<D, RPL, HW>(W, kp, -1, EV_FULL, lr);
     double* o = kp.pts_out + p * stride;

@@ -36,7 +36,7 @@ EXPORTS = [
     "mrbo_initial_guesses", "mrbo_dual_uniform", "mrbo_last_kernel_ms", "mrbo_gp_fit", "mrbo_gp_fit_theta",
     "mrbo_plan_info", "mrbo_last_gp_fit_ms", "mrbo_plan_set_order", "mrbo_base_solve", "mrbo_sga_step",
     "mrbo_kernel_times", "mrbo_merge_moments", "mrbo_adam_step", "mrbo_stochastic_solve",
-    "mrbo_plan_order_longest_first",
+    "mrbo_plan_order_longest_first", "mrbo_plan_create_batch",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM = 0, 1
@@ -92,6 +92,8 @@ def load():
     L.mrbo_device_count.restype = ctypes.c_int
     L.mrbo_plan_create.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.POINTER(ParamsDesc), ctypes.c_int32,
                                    ctypes.POINTER(_vp)]
+    L.mrbo_plan_create_batch.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.POINTER(ParamsDesc),
+                                         ctypes.c_int32, ctypes.POINTER(_vp)]
     L.mrbo_plan_destroy.argtypes = [_vp]
     L.mrbo_simulate_mc.argtypes = [_vp] + [_vp] * 12 + [ctypes.c_uint32, _vp]
     L.mrbo_simulate_ghq.argtypes = [_vp] + [_vp] * 13 + [ctypes.c_uint32, _vp]

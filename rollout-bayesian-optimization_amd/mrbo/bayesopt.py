@@ -32,10 +32,11 @@ from . import testfns as T
 from .decision_rules import EI, LCB, POI
 from .kernels import Matern52
 from .optimizers import Adam, StandardSGA
-from .rollout import simulate_trajectory_mc_batch
+from .rollout import simulate_trajectory_mc_batch, simulate_trajectory_mc_multi
 from .surrogates import FantasySurrogate, Surrogate
 from .trajectory import Trajectory, TrajectoryParameters
-from .utils import ExperimentSetup, gap, generate_batch, simple_regret, stochastic_solve_batch
+from .utils import (ExperimentSetup, gap, generate_batch, simple_regret, stochastic_solve_batch,
+                    stochastic_solve_multi)
 
 INITIAL_OBSERVATIONS = 5            # nonmyopic_bayesopt.jl:131
 METRICS = ["times", "gaps", "allocations", "simple_regret", "minimum_observations"]   # :191
@@ -141,6 +142,16 @@ def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_it
     x = np.clip(x, lbs[:, None], ubs[:, None])
     etos = simulate_trajectory_mc_batch(traj, tp, x, es.get_starts(), with_gradient=False, device=device).etos(
         with_gradient=False)
+    k, means = pick_restart(sur, x, etos, lbs, ubs, incumbent)
+    if trace is not None:
+        trace.append(dict(batch=batch, x=x.copy(), means=means, pick=k))
+    return x[:, k].copy(), float(means[k])
+
+
+def pick_restart(sur, x, etos, lbs, ubs, incumbent):
+    """rollout_solve's choice among the restarts' final points x (d×R): the largest final ETO mean,
+    with incumbent=True never an already observed point while another restart ends elsewhere.
+    Returns (index, the means with non-finite ones at −inf)."""
     means = np.array([e.mean() for e in etos])
     means = np.where(np.isfinite(means), means, -np.inf)
     rank = means.copy()
@@ -149,17 +160,53 @@ def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_it
         w = ubs - lbs
         d = np.abs((x[:, :, None] - Xa[:, None, :]) / w[:, None, None]).max(axis=0).min(axis=1)
         rank = np.where(d > 1e-9, rank, -np.inf) if (d > 1e-9).any() else rank
-    k = int(np.argmax(rank))
-    if trace is not None:
-        trace.append(dict(batch=batch, x=x.copy(), means=means, pick=k))
-    return x[:, k].copy(), float(means[k])
+    return int(np.argmax(rank)), means
+
+
+def rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta, eta=0.01,
+                        device=0, solver="sga", incumbent=True):
+    """rollout_solve for S surrogates of equal size at once (the lockstep trials of run(...,
+    parallel_trials=k)): the same Sobol batch on each, its own incumbent restart, the outer ascent of
+    all S·R restarts with one rollout launch per SGA iteration (stochastic_solve_multi) and one for
+    the final ETO means.  Returns [(xnext, mean)] per surrogate, each what rollout_solve returns on
+    that surrogate alone."""
+    lbs, ubs = np.asarray(lbs, float), np.asarray(ubs, float)
+    batch = generate_batch(batch_size, lbs, ubs)
+    batches = [np.hstack([batch, incumbent_start(s, lbs, ubs)[:, None]]) if incumbent else batch for s in surs]
+    x0 = np.stack(batches, axis=2)                                     # d×R×S
+    tp = TrajectoryParameters(start=batch[:, 0], hypers=[theta], horizon=horizon, mc_iterations=mc_samples,
+                              use_low_discrepancy_sequence=True, spatial_lowerbounds=lbs, spatial_upperbounds=ubs)
+    es = ExperimentSetup(tp, number_of_starts=starts)
+    trajs = [Trajectory(s, FantasySurrogate(s, horizon), start=batch[:, 0], hypers=[theta], horizon=horizon)
+             for s in surs]
+    opts = [[StandardSGA(η=eta) if solver == "sga" else BoxAdam(lbs, ubs, η=eta) for _ in range(x0.shape[1])]
+            for _ in surs]
+    x, _ = stochastic_solve_multi(opts, surs, tp, es, x0, Ts=trajs, iterations=sgd_iterations, device=device)
+    x = np.clip(x, lbs[:, None, None], ubs[:, None, None])
+    brs = simulate_trajectory_mc_multi(trajs, tp, x, es.get_starts(), with_gradient=False, device=device)
+    out = []
+    for q, s in enumerate(surs):
+        xq = x[:, :, q]
+        k, means = pick_restart(s, xq, brs[q].etos(with_gradient=False), lbs, ubs, incumbent)
+        out.append((xq[:, k].copy(), float(means[k])))
+    return out
+
+
+def _check_parallel_trials(parallel_trials, reuse_surrogate):
+    k = int(parallel_trials)
+    if k < 1:
+        raise ValueError(f"parallel_trials = {parallel_trials}: at least 1")
+    if k > 1 and reuse_surrogate:
+        raise ValueError("parallel_trials > 1 needs reuse_surrogate=False: with the reused surrogate trial t inherits "
+                         "trial t-1's kernel and stale capacity buffer (Q3), a sequential dependence")
+    return k
 
 
 # ---- the experiment loop (nonmyopic_bayesopt.jl:120-300) -------------------------------------
 def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, mc_samples=200, batch_size=8,
         sgd_iterations=50, optimize=False, seed=1906, device=0, log=print, rules=("ei", "poi", "lcb"), eta=0.01,
         initial_observations=INITIAL_OBSERVATIONS, solver="sga", fmini_over_capacity=True, incumbent=True,
-        reuse_surrogate=True):
+        reuse_surrogate=True, parallel_trials=1):
     """The experiment loop; `rules` selects a subset of the reference's three acquisitions (all by
     default, as nonmyopic_bayesopt.jl), `eta` the StandardSGA step of the build-defined solver
     (default 0.01, StandardSGA's own default, optimizers.jl:9),
@@ -170,7 +217,13 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     reuse_surrogate=True (the reference, :233-235): one surrogate of capacity budget + initial for
     every rule and trial, reset! per trial -- the kernel carries over between trials, and fmini over
     the capacity buffer (Q3) sees the stale observations of the previous trial past the initial
-    design; False: a fresh surrogate per trial (the round-3 loop)."""
+    design; False: a fresh surrogate per trial (the round-3 loop).
+    parallel_trials=k > 1 (needs reuse_surrogate=False, else ValueError): up to k trials advance in
+    lockstep -- every budget step is ONE batched acquisition solve for their k surrogates (a
+    surrogate batch, rollout_solve_multi), then each trial conditions (and optionally runs MLE) on
+    its own surrogate.  The trials observe exactly what they observe one after another; `times`
+    records the batched solve's wall time for each of its trials."""
+    parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
     directory = os.path.join(output_dir, function_name)
@@ -196,7 +249,40 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
         if reuse_surrogate:
             sur.set_decision_rule(rule)                                   # :241
         log(f"Conducting experiments with acquisition = {acq}")
-        for trial in range(trials):
+        for t0_ in range(0, trials if parallel_trials > 1 else 0, parallel_trials):
+            chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
+            surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
+                              capacity=budget + initial_observations, decision_rule=rule, σn2=1e-6) for t in chunk]
+            for s in surs:
+                s.fmini_over_capacity = fmini_over_capacity
+            ell_starts = [float(s.ψ.lengthscale) for s in surs]
+            initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
+            rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
+            for b in range(budget):
+                t0 = time.perf_counter()
+                picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
+                                            theta, eta=eta, device=device, solver=solver, incumbent=incumbent)
+                dt = time.perf_counter() - t0
+                for s, r, (xnext, _), initial_best in zip(surs, rec, picks, initial_bests):
+                    r["times"][b] = dt
+                    observed_best = float(np.min(s.get_active_observations()))
+                    r["simple_regret"][b] = simple_regret(true_minimum, observed_best)
+                    r["gaps"][b] = gap(initial_best, observed_best, true_minimum)
+                    s.condition(xnext, float(testfn.f(xnext)))
+                    if optimize:
+                        from .mle import optimize as mle_optimize
+                        mle_optimize(s, KERNEL_LBS, KERNEL_UBS)
+                    r["minimum_observations"][b] = float(np.min(s.get_active_observations()))
+            for trial, s, r, ell_start in zip(chunk, surs, rec, ell_starts):
+                log(f"{acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, {r['times'].sum():.2f} s of solves")
+                for metric in METRICS:
+                    write_to_csv(os.path.join(directory, f"{acq}_{metric}"), r[metric])
+                results[(acq, trial)] = dict(times=r["times"], gaps=r["gaps"], simple_regret=r["simple_regret"],
+                                             minimum_observations=r["minimum_observations"],
+                                             X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
+                                             ell_start=ell_start, ell_end=float(s.ψ.lengthscale),
+                                             repeats=np.zeros(budget, dtype=bool))
+        for trial in range(trials if parallel_trials == 1 else 0):
             Xinit = initial_samples[trial]
             yinit = testfn(Xinit)
             if reuse_surrogate:
@@ -237,7 +323,7 @@ MYOPIC_RULES = {"ei": (EI, 0.0), "poi": (POI, 0.0), "lcb": (LCB, 2.0)}   # :151-
 
 def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed=1906, device=0, log=print,
                rules=("ei", "poi", "lcb"), optimize=True, initial_observations=INITIAL_OBSERVATIONS,
-               reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False):
+               reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False, parallel_trials=1):
     """myopic_bayesopt.jl's loop: per budget step xnext = multistart_base_solve!(sur, …; guesses =
     generate_initial_guesses(starts, lbs, ubs), θfixed) -- the deterministic multistart local solve of
     the analytic acquisition on the base surrogate (:224-233), here mrbo_base_solve on the device --
@@ -257,8 +343,11 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     projected Newton's stops on the faces explain a difference.
     no_repeat (diagnostic, build-defined; False = the reference's findmin): the best start whose
     minimiser is not an observed point (within 1e-6 of a box width) is taken, to test whether
-    re-observing a point explains a difference; every trial records its repeated observations."""
-    from .rbf_optim import base_solve_batch, findmin_candidates, multistart_base_solve
+    re-observing a point explains a difference; every trial records its repeated observations.
+    parallel_trials=k > 1 (needs reuse_surrogate=False, else ValueError): up to k trials advance in
+    lockstep, every budget step one mrbo_base_solve launch on their k surrogates (base_solve_multi)."""
+    from .rbf_optim import base_solve_batch, base_solve_multi, findmin_candidates, multistart_base_solve
+    parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     from .utils import generate_initial_guesses
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
@@ -285,7 +374,48 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
         if reuse_surrogate:
             sur.set_decision_rule(make_rule())                            # :208
         log(f"Conducting experiments with acquisition = {acq}")
-        for trial in range(trials):
+        for t0_ in range(0, trials if parallel_trials > 1 else 0, parallel_trials):
+            chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
+            surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
+                              capacity=capacity or budget + initial_observations, decision_rule=make_rule(),
+                              σn2=1e-6) for t in chunk]
+            ell_starts = [float(s.ψ.lengthscale) for s in surs]
+            initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
+            rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
+            reps = [np.zeros(budget, dtype=bool) for _ in chunk]
+            tol = 1e-6 * (ubs - lbs)[:, None]
+            for b in range(budget):
+                t0 = time.perf_counter()
+                w = (ubs - lbs) * solve_margin
+                xs_, fs_, _ = base_solve_multi(surs, lbs + w, ubs - w, guesses, [theta], device=device)
+                dt = time.perf_counter() - t0
+                for q, (s, r, initial_best) in enumerate(zip(surs, rec, initial_bests)):
+                    xq, fq = xs_[:, :, q], fs_[:, q]
+                    Xo = s.X[:, :s.observed]
+                    fresh = [i for i in range(xq.shape[1])
+                             if not (np.abs(Xo - xq[:, i:i + 1]) <= tol).all(axis=0).any()] if no_repeat else []
+                    xnext = (xq[:, fresh[findmin_candidates(xq[:, fresh], fq[fresh])]] if fresh
+                             else xq[:, findmin_candidates(xq, fq)]).copy()
+                    r["times"][b] = dt
+                    reps[q][b] = bool((np.abs(Xo - xnext[:, None]) <= tol).all(axis=0).any())
+                    observed_best = float(np.min(s.get_active_observations()))
+                    r["simple_regret"][b] = simple_regret(true_minimum, observed_best)
+                    r["gaps"][b] = gap(initial_best, observed_best, true_minimum)
+                    s.condition(xnext, float(testfn.f(xnext)))
+                    if optimize:
+                        from .mle import optimize as mle_optimize
+                        mle_optimize(s, KERNEL_LBS, KERNEL_UBS)
+                    r["minimum_observations"][b] = float(np.min(s.get_active_observations()))
+            for trial, s, r, ell_start, rp in zip(chunk, surs, rec, ell_starts, reps):
+                log(f"myopic {acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, "
+                    f"{r['times'].sum():.2f} s of solves")
+                for metric in METRICS:
+                    write_to_csv(os.path.join(directory, f"{acq}_{metric}"), r[metric])
+                results[(acq, trial)] = dict(times=r["times"], gaps=r["gaps"], simple_regret=r["simple_regret"],
+                                             minimum_observations=r["minimum_observations"],
+                                             X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
+                                             ell_start=ell_start, ell_end=float(s.ψ.lengthscale), repeats=rp)
+        for trial in range(trials if parallel_trials == 1 else 0):
             Xinit = initial_samples[trial]
             yinit = testfn(Xinit)
             if reuse_surrogate:
@@ -347,6 +477,9 @@ def parse(argv=None):
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--function-name", required=True, choices=sorted(TESTFNS))
     ap.add_argument("--sgd-iterations", type=int, default=50)
+    ap.add_argument("--parallel-trials", type=int, default=1,
+                    help="trials advanced in lockstep, one batched acquisition solve per budget step "
+                         "(> 1 runs a fresh surrogate per trial)")
     return ap.parse_args(argv)
 
 
@@ -354,7 +487,7 @@ def main(argv=None):
     a = parse(argv)
     run(a.function_name, a.output_dir, budget=a.budget, trials=a.trials, starts=a.starts, horizon=a.horizon,
         mc_samples=a.mc_samples, batch_size=a.batch_size, sgd_iterations=a.sgd_iterations, optimize=a.optimize,
-        seed=a.seed)
+        seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1)
 
 
 if __name__ == "__main__":

@@ -36,25 +36,75 @@ def from_device(t, shape):
     return t.detach().cpu().numpy().reshape(shape, order="F")
 
 
+SURROGATE_KEYS = ("X", "L", "c", "y", "kernel", "lengthscale", "fmini")   # + sigma_n2, period (optional)
+
+
 class RolloutPlan:
     """Device state for (surrogate, trajectory parameters)."""
 
     def __init__(self, X, L, c, y, kernel, lengthscale, sigma_n2, fmini, h, M, R, nstarts, lbs, ubs, theta,
                  device=0, period=1.0, **opts):
         self.lib = _lib.load()
+        self.S = 1
+        self._X, self._L, self._c, self._y = _f64(X), _f64(L), _f64(c), _f64(y)
+        self.d, self.N = self._X.shape
+        dp = ctypes.POINTER(ctypes.c_double)
+        sd = _lib.SurrogateDesc(self.d, self.N, int(kernel), float(lengthscale), float(sigma_n2), float(fmini),
+                                self._X.ctypes.data_as(dp), self._L.ctypes.data_as(dp), self.N,
+                                self._c.ctypes.data_as(dp), self._y.ctypes.data_as(dp), float(period))
+        pd = self._params(h, M, R, nstarts, lbs, ubs, theta, device, opts)
+        h_ = ctypes.c_void_p()
+        _lib.check(self.lib.mrbo_plan_create(ctypes.byref(sd), ctypes.byref(pd), int(device), ctypes.byref(h_)))
+        self.handle = h_
+
+    @classmethod
+    def from_surrogates(cls, surrogates, h, M, R, nstarts, lbs, ubs, theta, device=0, **opts):
+        """A surrogate batch (mrbo_plan_create_batch): ONE plan and one launch per call for the S base
+        surrogates of `surrogates`, each a mapping with X (d×N), L, c, y, kernel, lengthscale, fmini
+        and optionally sigma_n2 (default 1e-6) and period (default 1).  They share d, N, kernel and
+        sigma_n2; R is the number of restarts PER surrogate, and everything else is shared.  Inputs
+        and outputs carry the surrogate index slowest (x0s d×R×S, values M×R×S, ...); block q of every
+        output is bit-identical to a plain plan on surrogate q."""
+        self = cls.__new__(cls)
+        self.lib = _lib.load()
+        surrogates = list(surrogates)
+        if not surrogates:
+            raise ValueError("from_surrogates needs at least one surrogate")
+        for q, s in enumerate(surrogates):
+            missing = [k for k in SURROGATE_KEYS if k not in s]
+            if missing:
+                raise ValueError(f"surrogate {q} lacks {missing}")
+        self.S = len(surrogates)
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._keep = []     # the host arrays the descriptors point into, alive until the create returns
+        sds = (_lib.SurrogateDesc * self.S)()
+        for q, s in enumerate(surrogates):
+            X, L, c, y = _f64(s["X"]), _f64(s["L"]), _f64(s["c"]).ravel(), _f64(s["y"]).ravel()
+            if X.ndim != 2 or L.shape != (X.shape[1], X.shape[1]) or c.size != X.shape[1] or y.size != X.shape[1]:
+                raise ValueError(f"surrogate {q}: X is {X.shape}, L {L.shape}, c {c.size}, y {y.size}")
+            self._keep.append((X, L, c, y))
+            sds[q] = _lib.SurrogateDesc(X.shape[0], X.shape[1], int(s["kernel"]), float(s["lengthscale"]),
+                                        float(s.get("sigma_n2", 1e-6)), float(s["fmini"]), X.ctypes.data_as(dp),
+                                        L.ctypes.data_as(dp), X.shape[1], c.ctypes.data_as(dp), y.ctypes.data_as(dp),
+                                        float(s.get("period", 1.0)))
+        self._X, self._L, self._c, self._y = self._keep[0]
+        self.d, self.N = self._X.shape
+        pd = self._params(h, M, R, nstarts, lbs, ubs, theta, device, opts)
+        h_ = ctypes.c_void_p()
+        _lib.check(self.lib.mrbo_plan_create_batch(sds, self.S, ctypes.byref(pd), int(device), ctypes.byref(h_)))
+        self.handle = h_
+        return self
+
+    def _params(self, h, M, R, nstarts, lbs, ubs, theta, device, opts):
+        """mrbo_params_t of the plan (and the plan's own copies of the sizes)."""
         o = dict(DEFAULTS)
         o.update(opts)
         self.opts = o
-        self._X, self._L, self._c, self._y = _f64(X), _f64(L), _f64(c), _f64(y)
-        self.d, self.N = self._X.shape
         self.h, self.M, self.R, self.nstarts = int(h), int(M), int(R), int(nstarts)
         self._lbs, self._ubs = _f64(lbs).ravel(), _f64(ubs).ravel()
         self.theta = float(theta)
         self.device = device
         dp = ctypes.POINTER(ctypes.c_double)
-        sd = _lib.SurrogateDesc(self.d, self.N, int(kernel), float(lengthscale), float(sigma_n2), float(fmini),
-                                self._X.ctypes.data_as(dp), self._L.ctypes.data_as(dp), self.N,
-                                self._c.ctypes.data_as(dp), self._y.ctypes.data_as(dp), float(period))
         ck = _lib.COSTS[o["cost"]] if isinstance(o["cost"], str) else int(o["cost"])
         self._cost_w = _f64(o["cost_w"]).ravel() if ck else None
         if ck and self._cost_w.size != self.d:
@@ -65,9 +115,7 @@ class RolloutPlan:
                              float(o["f_tol"]), float(o["g_tol"]), float(o["htol"]), float(o["sigma_tol"]),
                              int(o["seed"]), int(o.get("sample_offset", 0)), int(o.get("samples_total", 0)),
                              ck, float(o["cost_c0"]), self._cost_w.ctypes.data_as(dp) if ck else None)
-        h_ = ctypes.c_void_p()
-        _lib.check(self.lib.mrbo_plan_create(ctypes.byref(sd), ctypes.byref(pd), int(device), ctypes.byref(h_)))
-        self.handle = h_
+        return pd
 
     def close(self):
         if getattr(self, "handle", None):
@@ -84,7 +132,7 @@ class RolloutPlan:
     def alloc_outputs(self, with_gradient=True, want_policy=False, want_obs=False, want_evals=True):
         torch = _torch()
         dev = f"cuda:{self.device}"
-        T = self.M * self.R
+        T = self.M * self.R * self.S
         out = dict(values=torch.empty(T, dtype=torch.float64, device=dev),
                    status=torch.empty(T, dtype=torch.int32, device=dev))
         if with_gradient:
@@ -126,7 +174,7 @@ class RolloutPlan:
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         W = 2 + 2 * self.d + 2
-        e = torch.empty(W * self.R, dtype=torch.float64, device=f"cuda:{self.device}")
+        e = torch.empty(W * self.R * self.S, dtype=torch.float64, device=f"cuda:{self.device}")
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self.lib.mrbo_eto_reduce(self.handle, p(out["values"]), p(out.get("grad_x")),
                                             p(out.get("grad_theta")), p(e), 0, ctypes.c_void_p(st.cuda_stream)))
@@ -137,7 +185,7 @@ class RolloutPlan:
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         W = 2 + 2 * self.d + 2
-        e = torch.empty(W * self.R, dtype=torch.float64, device=f"cuda:{self.device}")
+        e = torch.empty(W * self.R * self.S, dtype=torch.float64, device=f"cuda:{self.device}")
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(self.lib.mrbo_partial_moments(self.handle, p(out["values"]), p(out.get("grad_x")),
                                               p(out.get("grad_theta")), int(M_local), p(e), 0,
@@ -152,9 +200,9 @@ class RolloutPlan:
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         W = 2 + 2 * self.d + 2
         n = len(counts)
-        if gathered.numel() != n * W * self.R or not gathered.is_cuda:
-            raise ValueError(f"gathered must be a device tensor of {n}·{W}·{self.R} moments")
-        e = torch.empty(W * self.R, dtype=torch.float64, device=f"cuda:{self.device}")
+        if gathered.numel() != n * W * self.R * self.S or not gathered.is_cuda:
+            raise ValueError(f"gathered must be a device tensor of {n}·{W}·{self.R * self.S} moments")
+        e = torch.empty(W * self.R * self.S, dtype=torch.float64, device=f"cuda:{self.device}")
         c = (ctypes.c_int64 * n)(*[int(k) for k in counts])
         _lib.check(self.lib.mrbo_merge_moments(self.handle, n, ctypes.c_void_p(gathered.data_ptr()), c,
                                                ctypes.c_void_p(e.data_ptr()), 0, ctypes.c_void_p(st.cuda_stream)))
@@ -200,18 +248,19 @@ class RolloutPlan:
         return int(res[0]), int(res[1]), int(res[2])
 
     def eval_base(self, xs):
-        """eval(s, x, θ) at the columns of xs (d×P); returns (3+4d+d²)×P numpy."""
+        """eval(s, x, θ) at the columns of xs (d×P); returns (3+4d+d²)×P numpy -- on a surrogate
+        batch (S > 1) the S blocks, (3+4d+d²)×P×S."""
         torch = _torch()
         xs = _f64(xs)
         d, P = xs.shape
         stride = 3 + 4 * d + d * d
         dx = to_device(xs, f"cuda:{self.device}")
-        do = torch.empty(stride * P, dtype=torch.float64, device=f"cuda:{self.device}")
+        do = torch.empty(stride * P * self.S, dtype=torch.float64, device=f"cuda:{self.device}")
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.lib.mrbo_eval_base(self.handle, P, ctypes.c_void_p(dx.data_ptr()),
                                            ctypes.c_void_p(do.data_ptr()), 0, ctypes.c_void_p(st.cuda_stream)))
         torch.cuda.synchronize(self.device)
-        return from_device(do, (stride, P))
+        return from_device(do, (stride, P) if self.S == 1 else (stride, P, self.S))
 
     def last_kernel_ms(self):
         return self.lib.mrbo_last_kernel_ms(self.handle)
@@ -234,6 +283,10 @@ class RolloutPlan:
         refuses anything but a permutation (a duplicated index would run one trajectory on two waves
         at once and leave another unrun, its outputs undefined); check=False passes any order of the
         right length to the library (tests: the all-out-of-range guard)."""
+        if self.S > 1:   # a surrogate batch has no work order: the library's MRBO_ERR_UNSUPPORTED
+            _lib.check(self.lib.mrbo_plan_set_order(
+                self.handle, None if order is None else ctypes.c_void_p(order.data_ptr()),
+                0 if order is None else order.numel()))
         if order is None:
             _lib.check(self.lib.mrbo_plan_set_order(self.handle, None, 0))
             self._order = None
@@ -278,10 +331,11 @@ class RolloutPlan:
 
     def info(self):
         """Launch geometry: rows per lane, workgroups, waves per workgroup, batched start values,
-        specialised kernel, LDS bytes per workgroup, fantasy capacity of the kernel unit (FMAX)."""
-        v = (ctypes.c_int32 * 7)()
-        _lib.check(self.lib.mrbo_plan_info(self.handle, v, 7))
-        keys = ("rpl", "blocks", "waves_per_group", "batch", "spec", "lds_bytes", "fmax")
+        specialised kernel, LDS bytes per workgroup, fantasy capacity of the kernel unit (FMAX), base
+        surrogates S (1: a plain plan)."""
+        v = (ctypes.c_int32 * 8)()
+        _lib.check(self.lib.mrbo_plan_info(self.handle, v, 8))
+        keys = ("rpl", "blocks", "waves_per_group", "batch", "spec", "lds_bytes", "fmax", "S")
         return dict(zip(keys, (int(x) for x in v)))
 
 

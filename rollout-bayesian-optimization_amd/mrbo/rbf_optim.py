@@ -45,6 +45,40 @@ def base_solve_batch(surrogate, spatial_lbs, spatial_ubs, guesses, θfixed, devi
     return from_device(xmin, (d, n)), from_device(fmin, (n,)), from_device(evals, (_lib.NCOUNTERS, n))
 
 
+def base_solve_multi(surrogates, spatial_lbs, spatial_ubs, guesses, θfixed, device=0, **opts):
+    """base_solve_batch on S base surrogates in ONE launch (a surrogate batch,
+    RolloutPlan.from_surrogates): the same `guesses` (d×n) on each.  Returns (minimizers d×n×S,
+    minima n×S, work counters NCOUNTERS×n×S), block q bit-identical to base_solve_batch(surrogates[q],
+    ...); raises like base_solve_batch when any surrogate's solve reports a status."""
+    from .rollout import _plan_for_multi, raise_on_status
+    torch = _torch()
+    surrogates = list(surrogates)
+    S = len(surrogates)
+    guesses = np.asarray(guesses, dtype=np.float64)
+    if guesses.ndim == 1:
+        guesses = guesses.reshape(-1, 1)
+    d, n = guesses.shape
+    if S < 1 or d != surrogates[0].X.shape[0]:
+        raise ValueError(f"guesses are {guesses.shape}: d×n with the d of the {S} surrogates")
+    theta = float(np.asarray(θfixed, dtype=np.float64).ravel()[0])
+    plan = _plan_for_multi(surrogates, 0, 1, 1, 1, spatial_lbs, spatial_ubs, theta, device, opts)
+    dev = f"cuda:{device}"
+    dxs = to_device(guesses, dev)
+    xmin = torch.empty(d * n * S, dtype=torch.float64, device=dev)
+    fmin = torch.empty(n * S, dtype=torch.float64, device=dev)
+    status = torch.empty(n * S, dtype=torch.int32, device=dev)
+    evals = torch.empty(_lib.NCOUNTERS * n * S, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream(device)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    _lib.check(plan.lib.mrbo_base_solve(plan.handle, n, p(dxs), p(xmin), p(fmin), p(status), p(evals), 0,
+                                        ctypes.c_void_p(st.cuda_stream)))
+    torch.cuda.synchronize(device)
+    stv = from_device(status, (n, S))
+    if np.any(stv != 0):
+        raise_on_status(stv)
+    return from_device(xmin, (d, n, S)), from_device(fmin, (n, S)), from_device(evals, (_lib.NCOUNTERS, n, S))
+
+
 def findmin_candidates(xs, fs):
     """multistart_base_solve!'s selection (rbf_optim.jl:129-131): drop candidates whose minimiser has a
     NaN, then findmin over the minima (a NaN minimum sorts first, else the first minimum wins).

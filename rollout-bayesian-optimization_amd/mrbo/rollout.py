@@ -33,6 +33,53 @@ def _plan_for(s, h, M, R, nstarts, lbs, ubs, theta, device, opts):
     return p
 
 
+def surrogate_dict(s):
+    """The fields of a Surrogate that RolloutPlan.from_surrogates reads (its observed part)."""
+    n = s.observed
+    return dict(X=s.X[:, :n], L=s.L[:n, :n], c=s.c[:n], y=s.y[:n], kernel=s.ψ.kind, lengthscale=s.ψ.lengthscale,
+                sigma_n2=s.σn2, fmini=s.fmini(), period=s.ψ.period)
+
+
+def check_surrogate_batch(surrogates):
+    """Host-side shape check of a surrogate batch: the surrogates share the input dimension, the
+    number of observed points, the kernel family, σn2 and the decision rule (the plan carries one
+    rule).  Raises ValueError; returns (d, N)."""
+    if len(surrogates) < 1:
+        raise ValueError("a surrogate batch needs at least one surrogate")
+    s0 = surrogates[0]
+    d, N = s0.X.shape[0], s0.observed
+    g0 = s0.get_decision_rule()
+    for q, s in enumerate(surrogates[1:], start=1):
+        if s.X.shape[0] != d or s.observed != N:
+            raise ValueError(f"surrogate {q} has d = {s.X.shape[0]}, N = {s.observed}; surrogate 0 has d = {d}, N = {N}")
+        if s.ψ.kind != s0.ψ.kind or s.σn2 != s0.σn2:
+            raise ValueError(f"surrogate {q} differs from surrogate 0 in its kernel family or σn2")
+        g = s.get_decision_rule()
+        if g.rule_id != g0.rule_id or g.σtol != g0.σtol:
+            raise ValueError(f"surrogate {q} differs from surrogate 0 in its decision rule")
+    return d, N
+
+
+def _plan_for_multi(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts):
+    """_plan_for for a surrogate batch: one RolloutPlan.from_surrogates plan, cached on the
+    surrogates' identities and versions."""
+    check_surrogate_batch(ss)
+    g = ss[0].get_decision_rule()
+    opts = dict(opts)
+    opts.setdefault("rule", g.rule_id)
+    opts.setdefault("sigma_tol", g.σtol)
+    key = (tuple((id(s), s.version) for s in ss), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()),
+           tuple(np.asarray(ubs).ravel()), float(theta), device, tuple(sorted(opts.items())))
+    p = _PLANS.get(key)
+    if p is None:
+        p = RolloutPlan.from_surrogates([surrogate_dict(s) for s in ss], h, M, R, nstarts, lbs, ubs, theta,
+                                        device=device, **opts)
+        if len(_PLANS) > 16:
+            _PLANS.clear()
+        _PLANS[key] = p
+    return p
+
+
 def raise_on_status(status):
     st = np.asarray(status)
     bad = st[st != 0]
@@ -95,6 +142,67 @@ def simulate_trajectory_mc_batch(T, tp, x0s, inner_solve_xstarts, with_gradient=
     plan.simulate(dx0, drn, dxs, out, dual_y_dx=ddy, replay_x=drp)
     eto = plan.eto(out)
     return BatchResult(plan, out, eto)
+
+
+class _PlanView:
+    """The sizes BatchResult reads, for one surrogate's block of a surrogate-batch launch."""
+
+    def __init__(self, plan):
+        self.d, self.M, self.R, self.h = plan.d, plan.M, plan.R, plan.h
+
+
+def check_multi_x0s(x0s, S, d=None):
+    """x0s of a surrogate batch: d×R×S (d×S: one restart each).  Raises ValueError; returns the
+    float64 d×R×S array."""
+    x0s = np.asarray(x0s, dtype=np.float64)
+    if x0s.ndim == 2:
+        x0s = x0s[:, None, :]
+    if x0s.ndim != 3 or x0s.shape[2] != S or (d is not None and x0s.shape[0] != d):
+        raise ValueError(f"x0s must be d×R×S with S = {S}" + (f", d = {d}" if d is not None else "") +
+                         f"; got {x0s.shape}")
+    return x0s
+
+
+def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient=True, dual_y_dx=None,
+                                 replay_x=None, want_policy=False, want_obs=False, device=0, rnstream=None, **opts):
+    """simulate_trajectory_mc_batch for S trajectories on S DIFFERENT base surrogates (Ts) in ONE
+    kernel launch (RolloutPlan.from_surrogates): x0s is d×R×S -- R restarts per surrogate --, tp,
+    the MC stream and the inner starts are shared, dual_y_dx / replay_x are d×h×M×R×S.  Returns one
+    BatchResult per surrogate (views of the launch's device outputs), each bit-identical to
+    simulate_trajectory_mc_batch(Ts[q], tp, x0s[:, :, q], ...)."""
+    import torch
+    Ts = list(Ts)
+    S = len(Ts)
+    if S < 1:
+        raise ValueError("simulate_trajectory_mc_multi needs at least one trajectory")
+    d0, _ = check_surrogate_batch([T.s for T in Ts])
+    x0s = check_multi_x0s(x0s, S, d0)
+    if any(float(T.θ[0]) != float(Ts[0].θ[0]) for T in Ts):
+        raise ValueError("the trajectories of a surrogate batch share the decision-rule hyperparameter θ")
+    d, R, _ = x0s.shape
+    lbs, ubs = tp.get_spatial_bounds()
+    rn = tp.rnstream_sequence if rnstream is None else rnstream
+    M = rn.shape[0]
+    h = tp.horizon
+    for name, a in (("dual_y_dx", dual_y_dx), ("replay_x", replay_x)):
+        if a is not None and np.shape(a) != (d, max(h, 1), M, R, S):
+            raise ValueError(f"{name} must be d×h×M×R×S = {(d, max(h, 1), M, R, S)}; got {np.shape(a)}")
+    plan = _plan_for_multi([T.s for T in Ts], h, M, R, inner_solve_xstarts.shape[1], lbs, ubs, Ts[0].θ[0], device,
+                           opts)
+    dev = f"cuda:{device}"
+    drn = rn if isinstance(rn, torch.Tensor) else to_device(rn, dev)
+    out = plan.alloc_outputs(with_gradient=with_gradient, want_policy=want_policy, want_obs=want_obs)
+    plan.simulate(to_device(x0s, dev), drn, to_device(inner_solve_xstarts, dev), out,
+                  dual_y_dx=None if dual_y_dx is None else to_device(dual_y_dx, dev),
+                  replay_x=None if replay_x is None else to_device(replay_x, dev))
+    eto = plan.eto(out)
+    view = _PlanView(plan)
+    W = 2 + 2 * d + 2
+    res = []
+    for q in range(S):   # block q of every flat output: the surrogate index is the slowest
+        oq = {k: v[q * (v.numel() // S):(q + 1) * (v.numel() // S)] for k, v in out.items()}
+        res.append(BatchResult(view, oq, eto[q * W * R:(q + 1) * W * R]))
+    return res
 
 
 def simulate_trajectory_mc(T, tp, inner_solve_xstarts, resolutions, spatial_gradients_container=None,

@@ -144,6 +144,47 @@ def stochastic_solve(optimizer, surrogate, tp, es, start, T=None, iterations=50,
     return x[:, 0]
 
 
+def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iterations=50, device=0, **opts):
+    """stochastic_solve_batch for S surrogates at once: `starts` is d×R×S (R restarts on each
+    surrogate), `optimizers` S lists of R optimizers.  The loop of stochastic_solve_batch over the
+    S·R restarts with ONE batched rollout launch per iteration (simulate_trajectory_mc_multi); every
+    restart keeps its own optimizer state and eswavs stop flag, so surrogate q's restarts move
+    exactly as stochastic_solve_batch(optimizers[q], surrogates[q], tp, es, starts[:, :, q]) moves
+    them.  Returns (x d×R×S, history: per iteration, per surrogate, the R ETOs)."""
+    from .rollout import check_multi_x0s, simulate_trajectory_mc_multi
+    from .surrogates import FantasySurrogate
+    from .trajectory import Trajectory
+    surrogates = list(surrogates)
+    S = len(surrogates)
+    x = np.array(check_multi_x0s(starts, S), dtype=np.float64)
+    d, R, _ = x.shape
+    if len(optimizers) != S or any(len(o) != R for o in optimizers):
+        raise ValueError(f"optimizers must be {S} lists of {R} optimizers (one per surrogate and restart)")
+    if Ts is None:
+        Ts = [Trajectory(s, FantasySurrogate(s, tp.horizon), start=x[:, 0, q], hypers=tp.θ, horizon=tp.horizon)
+              for q, s in enumerate(surrogates)]
+    if len(Ts) != S:
+        raise ValueError(f"{len(Ts)} trajectories for {S} surrogates")
+    active = np.ones((R, S), dtype=bool)
+    history = []
+    for _ in range(iterations):
+        if not active.any():
+            break
+        brs = simulate_trajectory_mc_multi(Ts, tp, x, es.get_starts(), device=device, **opts)
+        etos = [br.etos() for br in brs]
+        history.append(etos)
+        for q in range(S):
+            for r in range(R):
+                if not active[r, q]:
+                    continue
+                e = etos[q][r]
+                if eswavs(e.gradient(), e.std_gradient() ** 2, tp.mc_iters):
+                    active[r, q] = False
+                    continue
+                optimizers[q][r].update(x[:, r, q], e.gradient())
+    return x, history
+
+
 def stochastic_solve_batch(optimizers, surrogate, tp, es, starts, T=None, iterations=50, device=0, **opts):
     """R restarts of the outer ascent at once: one batched rollout launch per SGA iteration;
     each restart keeps its own optimizer state and eswavs stop flag."""
