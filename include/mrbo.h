@@ -346,7 +346,10 @@ double mrbo_last_gp_fit_ms(void);
  * (0/1), compile-time specialised kernel (0 generic, 1 Matérn-5/2 + EI, 2 its half-wave form: N ≤ 32, d ≤ 4, h ≤ 3, 3 Matérn-5/2 + EI + quadratic cost), LDS bytes per workgroup,
  * fantasy capacity of the kernel unit (4: the FMAX = 4 units of h ≤ 3, d ≤ 8; else 6);
  * info[7] = S, the plan's base surrogates (1: a plain plan; info[1] stays the workgroups of a plain
- * launch, a surrogate batch launches ⌈info[1]/S⌉ × S).  Writes min(n, 8). */
+ * launch, a surrogate batch launches ⌈info[1]/S⌉ × S);
+ * info[8] = restart table (1: the step-0 evaluation at x0 and the factor of its draw run once per
+ * restart and every sample reads them; 0: every trajectory runs them -- MRBO_RESTART_TABLES=0 in the
+ * environment at plan creation, the half-wave kernel, N > 64).  Writes min(n, 9). */
 int mrbo_plan_info(const mrbo_plan_t* plan, int32_t* info, int32_t n);
 
 /* Work order of the plan's later mrbo_simulate_mc / mrbo_simulate_ghq launches (no reference

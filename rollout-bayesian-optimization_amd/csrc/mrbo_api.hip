@@ -66,6 +66,8 @@ struct mrbo_plan {
   double* dcost = nullptr;  // NonUniformCost table [lb (d), ub − lb (d), w (d)] (cost models only)
   double* dwork = nullptr;
   double* dytab = nullptr;  // batched starts: the launch's Y0(x_start) table (square layout, ytab_kernel)
+  double* drtab = nullptr;  // the launch's restart table (KParams::rtab), R·S rows; null: step 0 in place
+  int rtab_wg = 0;          // its writer workgroups per surrogate in the ytab_kernel launch
   double* dkxb = nullptr;   // batched starts, packed layouts: global start tables (start_tables_kernel)
   double* dgtab = nullptr;
   SurTab* dstab = nullptr;  // S > 1: the per-surrogate table (KParams::stab); dX0 ... dgtab hold S blocks
@@ -795,6 +797,14 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
     if (waves1 >= waves0 && waves1 > 0) { P->batch = 1; P->wpg = wpg1; P->blocks = blocks1; P->smem = smem1; }
   }
   if (!P->batch) { P->wpg = wpg0; P->blocks = blocks0; P->smem = smem0; }
+  // The restart table (step 0 of a trajectory once per restart instead of once per sample): the
+  // square layout's full-wave kernels, generic and specialised.  The half-wave kernel and the
+  // N > 64 layouts keep step 0 in place.  MRBO_RESTART_TABLES=0 keeps it in place everywhere (A/B
+  // runs and tests); mrbo_plan_info reports which it is
+  const char* rt = getenv("MRBO_RESTART_TABLES");
+  const bool use_rtab = ks.square && P->spec != 2 && p->R > 0 && !(rt && rt[0] == '0');
+  // a wave per restart, in workgroups of the rollout launch's shape
+  P->rtab_wg = use_rtab ? std::min(256, (p->R + P->wpg - 1) / P->wpg) : 0;
   // packed layouts: the start tables live in global memory (no LDS, no occupancy cost)
   if (!ks.square && P->xs_lds && ns <= 64) P->batch = 1;
   if (!waves0 ||
@@ -821,6 +831,8 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
             (!P->batch || ks.square ||
              (hipMalloc(&P->dkxb, sizeof(double) * (size_t)P->NR * ns * S) == hipSuccess &&
               hipMalloc(&P->dgtab, sizeof(double) * (size_t)ns * ng * S) == hipSuccess)) &&
+            (!use_rtab ||
+             hipMalloc(&P->drtab, sizeof(double) * (size_t)rtab_stride(d, P->NR) * p->R * S) == hipSuccess) &&
             hipMalloc(&P->dqueue, sizeof(int) * MRBO_QUEUE_INTS * S) == hipSuccess &&
             (S == 1 || hipMalloc(&P->dstab, sizeof(SurTab) * S) == hipSuccess) &&
             (P->p.cost == MRBO_COST_NONE || hipMalloc(&P->dcost, sizeof(double) * 3 * d) == hipSuccess);
@@ -864,6 +876,7 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
 int mrbo_plan_destroy(mrbo_plan_t* P) {
   if (!P) return MRBO_OK;
   for (void* b : {(void*)P->dX0, (void*)P->dc0, (void*)P->dLinv, (void*)P->dlbs, (void*)P->dubs, (void*)P->dwork, (void*)P->dytab,
+                  (void*)P->drtab,
                   (void*)P->dkxb, (void*)P->dgtab, (void*)P->dqueue, (void*)P->dcost, (void*)P->dstab, P->oorder})
     if (b) (void)hipFree(b);
   for (auto& b : P->stage)
@@ -949,7 +962,10 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
     launch_tables(d, P->RPL, P->fx, P->p.nstarts, st, kp);
     HIP_TRY(hipGetLastError());
   }
-  if (P->batch && P->RPL == 1) {   // square layout: the launch's Y0(x_start) table, written once
+  kp.rtab = P->drtab;
+  kp.rtab_wg = P->drtab ? P->rtab_wg : 0;
+  // square layout: the launch's Y0(x_start) table and its restart table, written once
+  if (P->RPL == 1 && (P->batch || kp.rtab)) {
     launch_ytab(d, P->fx, P->spec, dim3(P->wpg * WAVE), P->smem, st, kp);
     HIP_TRY(hipGetLastError());
   }
@@ -1516,8 +1532,9 @@ int mrbo_plan_order_longest_first(mrbo_plan_t* P, const int64_t* evals, int32_t*
 
 int mrbo_plan_info(const mrbo_plan_t* P, int32_t* info, int32_t n) {
   if (!P || !info || n < 0) return fail(MRBO_ERR_ARG, "bad arguments");
-  const int32_t v[8] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6, P->S};
-  for (int i = 0; i < n && i < 8; ++i) info[i] = v[i];
+  const int32_t v[9] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6, P->S,
+                        P->drtab ? 1 : 0};
+  for (int i = 0; i < n && i < 9; ++i) info[i] = v[i];
   return MRBO_OK;
 }
 

@@ -136,7 +136,19 @@ struct KParams {
   // (a pointer to a table, not array members: see cost_tab)
   const SurTab* stab;
   int S;
+  // Restart table (square full-wave layout; null: every trajectory evaluates step 0 itself): row
+  // r + blockIdx.y·R holds what step 0 of restart r leaves behind -- the EV_DRAW evaluation of the
+  // base surrogate at x0_r and the factor of its draw, the same for all M samples.  Written by
+  // rtab_wg further workgroups of the ytab_kernel launch, read by trajectory() at k = 0
+  double* rtab;         // [R·S][rtab_stride(d, NR)]
+  int rtab_wg;
 };
+
+// one row of KParams::rtab: w (NR doubles, one per lane), then the header
+//   [σ², μ, G00, σ, factor failed (0 / 1), ∇μ (d), ∇σ (d), packed factor of Dk(0) − G ((d+1)(d+2)/2)]
+enum { RT_VAR = 0, RT_MU = 1, RT_G00 = 2, RT_SIG = 3, RT_FAIL = 4, RT_GMU = 5 };
+__host__ __device__ constexpr int rtab_header(int d) { return RT_GMU + 2 * d + (d + 1) * (d + 2) / 2; }
+__host__ __device__ constexpr long long rtab_stride(int d, int NR) { return NR + ((rtab_header(d) + 1) & ~1); }
 
 
 // ---- packed L0⁻¹ layout: column j holds rows j..Npad-1 contiguously ----------------------

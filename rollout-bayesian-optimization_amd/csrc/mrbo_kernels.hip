@@ -146,7 +146,8 @@ void MRBO_SFX(launch_rollout_d)(int rpl, int spec, dim3 g, dim3 b, size_t sm, hi
 
 // The Y0 table of a square-layout launch (rows per lane 1) with batched starts: ONE workgroup per
 // base surrogate (kp.S: 1 for a plain plan) of the rollout launch's shape (b, sm) and kernel variant
-// (spec as launch_rollout_d) writes it just before the rollout kernel, on the same stream
+// (spec as launch_rollout_d) writes it just before the rollout kernel, on the same stream; the
+// full-wave kernels' launch has kp.rtab_wg further workgroups per surrogate for the restart table
 void MRBO_SFX(launch_ytab_d)(int spec, dim3 b, size_t sm, hipStream_t st, const KParams& kp) {
 #if MRBO_HAS_HALF
   if (spec == 2) {
@@ -157,16 +158,16 @@ void MRBO_SFX(launch_ytab_d)(int spec, dim3 b, size_t sm, hipStream_t st, const 
 #if defined(MRBO_AB_MIN) && (defined(MRBO_AB_COST) || MRBO_AB_RPL != 1)
   (void)spec; (void)b; (void)sm; (void)st; (void)kp;
 #elif defined(MRBO_AB_MIN) && defined(MRBO_AB_GENERIC)
-  hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 0>), dim3(1, kp.S), b, sm, st, kp);
+  hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 0>), dim3(1 + kp.rtab_wg, kp.S), b, sm, st, kp);
 #elif defined(MRBO_AB_MIN)
-  if constexpr (has_spec(MRBO_D, 1)) hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 1>), dim3(1, kp.S), b, sm, st, kp);
+  if constexpr (has_spec(MRBO_D, 1)) hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 1>), dim3(1 + kp.rtab_wg, kp.S), b, sm, st, kp);
 #else
   if constexpr (has_spec(MRBO_D, 1))
     if (spec == 1) {
-      hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 1>), dim3(1, kp.S), b, sm, st, kp);
+      hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 1>), dim3(1 + kp.rtab_wg, kp.S), b, sm, st, kp);
       return;
     }
-  hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 0>), dim3(1, kp.S), b, sm, st, kp);
+  hipLaunchKernelGGL((ytab_kernel<MRBO_D, 1, 0>), dim3(1 + kp.rtab_wg, kp.S), b, sm, st, kp);
 #endif
 }
 

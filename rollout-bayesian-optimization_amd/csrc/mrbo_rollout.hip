@@ -1256,14 +1256,14 @@ __device__ __forceinline__ int condition(WaveCtx<D, RPL, HW>& W, const KParams& 
   return 0;
 }
 
-// gp_draw with gradient (r_b_s.jl:588-611): [y;∇y] = [μ;∇μ] + chol(Dk(0) − G)·z.
-// Every lane computes the (d+1)² Cholesky redundantly (wave-uniform registers).
+// Packed lower Cholesky factor Lc of Dk(0) − G (U_G of the EV_DRAW evaluation before it), every
+// lane redundantly (wave-uniform registers).  Returns 2 at the first non-positive pivot.  One
+// function for draw and for the restart table's writer (restart_rows): the same bits in both.
 template <int D, int RPL, int HW>
-__device__ __forceinline__ int draw(WaveCtx<D, RPL, HW>& W, const KParams& kp, const double* z, double& yv, double* gy) {
+__device__ __forceinline__ int draw_factor(WaveCtx<D, RPL, HW>& W, double (&Lc)[Lay<D, RPL, HW>::NG]) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1;
   const double* U = W.U;
-  double Lc[D1 * (D1 + 1) / 2];
 #define TRI(i, j) ((i) * ((i) + 1) / 2 + (j))
 #pragma unroll
   for (int j = 0; j < D1; ++j) {
@@ -1283,6 +1283,28 @@ __device__ __forceinline__ int draw(WaveCtx<D, RPL, HW>& W, const KParams& kp, c
       for (int k = 0; k < j; ++k) t -= Lc[TRI(i, k)] * Lc[TRI(j, k)];
       Lc[TRI(i, j)] = t * ij;
     }
+  }
+#undef TRI
+  return 0;
+}
+
+// gp_draw with gradient (r_b_s.jl:588-611): [y;∇y] = [μ;∇μ] + chol(Dk(0) − G)·z.
+// hdr: null, or the restart-table header of this trajectory's restart (k = 0): the factor and
+// whether it failed come from there instead of being computed.
+template <int D, int RPL, int HW>
+__device__ __forceinline__ int draw(WaveCtx<D, RPL, HW>& W, const KParams& kp, const double* z, double& yv, double* gy,
+                                    const double* hdr = nullptr) {
+  using Ly = Lay<D, RPL, HW>;
+  constexpr int D1 = Ly::D1;
+  const double* U = W.U;
+  double Lc[Ly::NG];
+#define TRI(i, j) ((i) * ((i) + 1) / 2 + (j))
+  if (hdr) {
+    if (hdr[RT_FAIL] != 0.0) return 2;
+#pragma unroll
+    for (int i = 0; i < Ly::NG; ++i) Lc[i] = hdr[RT_GMU + 2 * D + i];
+  } else if (draw_factor<D, RPL, HW>(W, Lc)) {
+    return 2;
   }
   double out[D1];
   out[0] = U[Ly::U_SC + SC_MU];
@@ -2275,6 +2297,40 @@ __device__ __forceinline__ void rich_eval_at(WaveCtx<D, RPL, HW>& W, const KPara
   evaluate<D, RPL, HW>(W, kp, j - 1, EV_RICH, lr);
 }
 
+// Step 0 of restart r (global: r + s·R in a surrogate batch) from the launch's restart table
+// (KParams::rtab, written by restart_rows): restores what the EV_DRAW evaluation on the base
+// surrogate at x0_r leaves for the status test, the observable, draw and condition -- σ², μ, G00, σ,
+// ∇μ, ∇σ in U, w and the base coefficients in lr -- and stages the row's header in W.red, where
+// draw finds the factor.  Everything else that evaluation writes is overwritten by the next
+// evaluation before it is read.
+template <int D, int RPL, int HW>
+__device__ __forceinline__ void restart_row_load(WaveCtx<D, RPL, HW>& W, const KParams& kp, int r, LaneRes<D, RPL, HW>& lr) {
+  using Ly = Lay<D, RPL, HW>;
+  static_assert(RPL == 1 && HW == 1, "restart table: square full-wave layout");
+  static_assert(rtab_header(D) <= Ly::REDN, "restart-table header staged in the reduction area");
+  double* U = W.U;
+  double* red = W.red;
+  const int lane = W.ln();
+  const double* row = kp.rtab + (long long)r * rtab_stride(D, Ly::NR);
+  lr.w[0] = row[lane];
+  lr.cb[0] = W.C[lane];
+#pragma unroll
+  for (int a = 0; a < D; ++a) lr.P[0][a] = 0.0;
+  for (int q = lane; q < rtab_header(D); q += WAVE) red[q] = row[Ly::NR + q];
+  wave_sync();
+  if (lane == 0) {
+    U[Ly::U_SC + SC_VAR] = red[RT_VAR];
+    U[Ly::U_SC + SC_MU] = red[RT_MU];
+    U[Ly::U_G] = red[RT_G00];
+    U[Ly::U_SC + SC_SIG] = red[RT_SIG];
+  }
+  if (lane < D) {
+    U[Ly::U_GMU + lane] = red[RT_GMU + lane];
+    U[Ly::U_GSIG + lane] = red[RT_GMU + D + lane];
+  }
+  wave_sync();
+}
+
 // ================================================================================
 // One trajectory.
 // ================================================================================
@@ -2331,7 +2387,14 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
       }
     }
     if (kp.policy && lane < D) kp.policy[(long long)lane + D * (k + (long long)(h + 1) * (m + (long long)M * r))] = U[Ly::U_X + lane];
-    evaluate<D, RPL, HW>(W, kp, S, EV_DRAW, lr);
+    // step 0 is the same for every sample of a restart: with the launch's restart table its
+    // evaluation and the factor of its draw are read, not computed (restart_row_load)
+    bool tabled = false;
+    if constexpr (Ly::SQ && HW == 1) {
+      tabled = (k == 0) && kp.rtab != nullptr;
+      if (tabled) restart_row_load<D, RPL, HW>(W, kp, r, lr);
+    }
+    if (!tabled) evaluate<D, RPL, HW>(W, kp, S, EV_DRAW, lr);
     if (U[Ly::U_SC + SC_VAR] < 0.0) { st |= 1; break; }
     if (k == 0 && lane < D) U[Ly::U_GMU0 + lane] = U[Ly::U_GMU + lane];
     double yv, gy[D];
@@ -2347,7 +2410,7 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
       double z[D1];
 #pragma unroll
       for (int a = 0; a < D1; ++a) z[a] = kp.rn[(long long)m + (long long)M * a + (long long)M * D1 * k];
-      st |= draw<D, RPL, HW>(W, kp, z, yv, gy);
+      st |= draw<D, RPL, HW>(W, kp, z, yv, gy, tabled ? W.red : nullptr);
       if (st) break;
     }
     wave_sync();
@@ -2619,10 +2682,64 @@ __device__ __forceinline__ void stage_linv(const KParams& kp, double* smem) {
   __syncthreads();
 }
 
-// The Y0(x_start) table of the square layouts (kp.batch), written ONCE per launch: one workgroup of
-// the rollout launch's shape and LDS size, launched just before rollout_kernel on the same stream,
-// runs the rollout prologue's own code with store_y (so its rows are the bits the rollout
-// workgroups' own Gram tables come from).
+// The restart table of a launch (KParams::rtab): workgroups 1..rtab_wg of the ytab_kernel launch, a
+// wave per restart, run step 0 of a trajectory up to the sample's draw -- the rollout's own
+// evaluate(EV_DRAW) on the base surrogate at x0_r and draw's own factor (draw_factor), compiled
+// in the same unit -- and store what restart_row_load restores.  x0s is read on the device, on the
+// launch stream: a later launch with other x0 rewrites every row it reads.
+template <int D, int RPL, int HW>
+__device__ __forceinline__ void restart_rows(const KParams& kp, double* smem) {
+  using Ly = Lay<D, RPL, HW>;
+  static_assert(RPL == 1 && HW == 1, "restart table: square full-wave layout");
+  stage_linv<D, RPL, HW>(kp, smem);
+  WaveCtx<D, RPL, HW> W;
+  wave_setup<D, RPL, HW>(W, kp, smem, threadIdx.x / WAVE);
+  surrogate_constants<D, RPL, HW>(W, kp);
+  wave_sync();
+#ifdef MRBO_STAMPS
+  W.tlast = __builtin_amdgcn_s_memtime();
+#endif
+  double* U = W.U;
+  const int lane = W.ln();
+  const int wpg = blockDim.x / WAVE;
+  LaneRes<D, RPL, HW> lr;
+  for (int r = ((int)blockIdx.x - 1) * wpg + (int)threadIdx.x / WAVE; r < kp.R; r += ((int)gridDim.x - 1) * wpg) {
+    const long long rg = r + (long long)blockIdx.y * kp.R;   // surrogate batch: block blockIdx.y of the restarts
+    if (kp.skip_active && kp.skip_active[rg] == 0) continue;   // a stopped restart: no trajectory reads its row
+    W.C[lane] = kp.c0[lane];
+    if (lane == 0) U[Ly::U_FMIN] = U[Ly::U_KC + KC_FMINB];
+    if (lane < D) U[Ly::U_X + lane] = kp.x0s[rg * D + lane];
+    wave_sync();
+    evaluate<D, RPL, HW>(W, kp, -1, EV_DRAW, lr);
+    double Lc[Ly::NG];
+#pragma unroll
+    for (int i = 0; i < Ly::NG; ++i) Lc[i] = 0.0;
+    const int failed = draw_factor<D, RPL, HW>(W, Lc);
+    double* row = kp.rtab + rg * rtab_stride(D, Ly::NR);
+    row[lane] = lr.w[0];
+    double* hdr = row + Ly::NR;
+    if (lane == 0) {
+      hdr[RT_VAR] = U[Ly::U_SC + SC_VAR];
+      hdr[RT_MU] = U[Ly::U_SC + SC_MU];
+      hdr[RT_G00] = U[Ly::U_G];
+      hdr[RT_SIG] = U[Ly::U_SC + SC_SIG];
+      hdr[RT_FAIL] = failed ? 1.0 : 0.0;
+#pragma unroll
+      for (int i = 0; i < Ly::NG; ++i) hdr[RT_GMU + 2 * D + i] = Lc[i];
+    }
+    if (lane < D) {
+      hdr[RT_GMU + lane] = U[Ly::U_GMU + lane];
+      hdr[RT_GMU + D + lane] = U[Ly::U_GSIG + lane];
+    }
+    wave_sync();
+  }
+}
+
+// The launch tables of the square layouts, written ONCE per launch by workgroups of the rollout
+// launch's shape and LDS size, launched just before rollout_kernel on the same stream.  Workgroup 0
+// (kp.batch): the Y0(x_start) table, by the rollout prologue's own code with store_y (so its rows
+// are the bits the rollout workgroups' own Gram tables come from).  Workgroups 1..kp.rtab_wg
+// (kp.rtab, full wave): the restart table (restart_rows).
 template <int D, int RPL, int SPEC, int HW = 1>
 __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RPL, HW>::waves_per_simd)) ytab_kernel(KParams kp_in) {
   KParams kp = kp_in;
@@ -2631,8 +2748,14 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   extern __shared__ __attribute__((aligned(16))) double smem[];
   using Ly = Lay<D, RPL, HW>;
   if constexpr (Ly::SQ) {
-    stage_linv<D, RPL, HW>(kp, smem);
-    stage_start_tables<D, RPL, HW>(kp, smem, true);
+    if (blockIdx.x == 0) {
+      if (kp.batch) {
+        stage_linv<D, RPL, HW>(kp, smem);
+        stage_start_tables<D, RPL, HW>(kp, smem, true);
+      }
+      return;
+    }
+    if constexpr (HW == 1) restart_rows<D, RPL, HW>(kp, smem);
   }
 }
 

@@ -95,11 +95,19 @@ def launch_flops(evals, N, d, h, info=None, nstarts=0):
     info: RolloutPlan.info() of the launch.  With batched start values the counters still count
     every start point as a value evaluation (as the oracle does); those h·nstarts evaluations per
     trajectory are charged at the batched pass's cost instead, plus the start tables (staged once
-    per workgroup for the square layout, once per launch for the packed ones)."""
+    per workgroup for the square layout, once per launch for the packed ones).  With the restart
+    table (info["restart_tables"]) the step-0 draw runs once per restart -- the last axis of evals,
+    R·S of a surrogate batch -- and not once per trajectory."""
     import numpy as np
-    e = np.asarray(evals, dtype=np.float64).reshape(NCOUNTERS, -1)
+    ev = np.asarray(evals, dtype=np.float64)
+    e = ev.reshape(NCOUNTERS, -1)
     ntraj = e.shape[1]
     draws = sum(f_draw(N, k, d) for k in range(h + 1))
+    draw0_saved = 0.0
+    if info is not None and info.get("restart_tables"):
+        if ev.ndim != 3:
+            raise ValueError("launch_flops: evals of shape (NCOUNTERS, M, R) needed to count the restarts")
+        draw0_saved = float(ntraj - ev.shape[2]) * f_draw(N, 0, d)
     tot = e.sum(axis=1)
     extra = 0.0
     if info is not None and info.get("batch") and nstarts:
@@ -108,4 +116,4 @@ def launch_flops(evals, N, d, h, info=None, nstarts=0):
         nf_solve = (1 + h) / 2.0
         tables = info["blocks"] if info.get("rpl", 1) == 1 else 1
         extra = nb * f_batch_start(N, nf_solve, d) + tables * nstarts * f_start_table(N, d)
-    return float(trajectory_flops(tot, N, d, h) + ntraj * draws + extra)
+    return float(trajectory_flops(tot, N, d, h) + (ntraj * draws - draw0_saved) + extra)
