@@ -317,12 +317,33 @@ int mrbo_base_solve(mrbo_plan_t* plan, int32_t n, const double* xstarts, double*
  * per-device pool; 32 < N ≤ 64 with d ≤ 16 and without L_out / c_out runs the register kernel
  * (one candidate per workgroup, no workspace); otherwise 32 < N ≤ 80 with d ≤ 16 runs the LDS
  * kernel (the candidate in LDS, no workspace); d > 16 runs the tile kernel.  A configuration whose LDS (dynamic + the kernel's static arrays) exceeds
- * the device limit fails with MRBO_ERR_UNSUPPORTED.  Synchronises the stream before returning. */
+ * the device limit fails with MRBO_ERR_UNSUPPORTED.  Synchronises the stream before returning.
+ * This is the S = 1 case of mrbo_gp_fit_multi (one code path, one launch of grid (P, 1)). */
 int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t P, int32_t nt, const double* thetas, double* ll,
                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream);
 /* mrbo_gp_fit_theta with nt = 1: ells[p] = ℓ_p, dll[p] = ∂ll/∂ℓ (Periodic: p = s->period). */
 int mrbo_gp_fit(const mrbo_surrogate_t* s, int32_t P, const double* ells, double* ll, double* dll, int32_t* status,
                 double* L_out, double* c_out, uint32_t flags, void* stream);
+
+/* mrbo_gp_fit_theta for S data sets s[0..S-1] with P hyperparameter vectors each, in ONE launch of
+ * grid (P, S) -- the refits of k lockstep BO trials (no reference counterpart: optimize! runs per
+ * surrogate, r_b_s.jl:805-829).  The data sets share d, N, kernel and σn2 and differ in X, y and,
+ * for Periodic with nt = 1, in period; lengthscale, L, c and fmini are unused.  The data set index
+ * is slowest everywhere, as in mrbo_plan_create_batch: thetas nt×P×S, ll and status P×S, grad
+ * nt×P×S, L_out N×N×P×S and c_out N×P×S (both optional).  Workgroup (p, q) fits data set q at
+ * θ_{p,q} with the code of a plain call: block q of every output is bit-identical to
+ * mrbo_gp_fit_theta(&s[q], P, nt, thetas + q·nt·P, ...), and a PosDefException in one slot
+ * (status 1, NaN ll and grad) leaves every other slot of the launch as it is.  Kernel selection,
+ * the LDS limit, pointer and flag conventions are those of mrbo_gp_fit_theta; the tile kernel's
+ * workspace is its per-candidate size × P·S from the per-device pool (MRBO_ERR_NOMEM when that
+ * fails).  All S data sets (and θ of a host call) go to the device in one copy, the small
+ * outputs of a host call come back in one.  MRBO_ERR_ARG, before any device call: S < 1, P < 1,
+ * an entry without X or y, an entry whose d, N, kernel or σn2 differs from s[0]'s, nt outside the
+ * kernel's range, Periodic with nt = 1 and a non-positive period in any entry.  N > 512 (or
+ * S > 65535) is MRBO_ERR_UNSUPPORTED.  Synchronises the stream before returning;
+ * mrbo_last_gp_fit_ms reports the launch. */
+int mrbo_gp_fit_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas, double* ll,
+                      double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream);
 
 /* Host helpers (HOST memory). */
 int mrbo_rnstream(int32_t M, int32_t d, int32_t H, double* out);                 /* M×(d+1)×H */
@@ -337,7 +358,7 @@ double mrbo_last_kernel_ms(mrbo_plan_t* plan);
  * number written (≥ 0) or a negative mrbo_err_t.  Waits for those launches.                    */
 int mrbo_kernel_times(mrbo_plan_t* plan, int32_t n, double* ms);
 
-/* Kernel time of the last mrbo_gp_fit launch (HIP events around it), milliseconds; -1 before
+/* Kernel time of the last mrbo_gp_fit / _theta / _multi launch (HIP events around it), milliseconds; -1 before
  * the first call.  Process-wide (the last call on any stream). */
 double mrbo_last_gp_fit_ms(void);
 

@@ -1366,40 +1366,56 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   return MRBO_OK;
 }
 
-int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const double* thetas, double* ll,
-                      double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
+// mrbo_gp_fit_multi and, as its S = 1 case, mrbo_gp_fit_theta (`multi` only words the messages)
+static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_t nt, const double* thetas, double* ll,
+                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream,
+                       bool multi) {
   if (!s || !thetas || !ll || !grad || !status || np < 1) return fail(MRBO_ERR_ARG, "null argument");
+  if (ns < 1) return fail(MRBO_ERR_ARG, "gp_fit_multi: S=%d", ns);
   const int d = s->d, N = s->N;
-  if (d < 1 || N < 1 || !s->X || !s->y) return fail(MRBO_ERR_ARG, "bad surrogate (d=%d N=%d)", d, N);
+  // every argument check comes before the first HIP call
+  for (int q = 0; q < ns; ++q) {
+    if (s[q].d < 1 || s[q].N < 1 || !s[q].X || !s[q].y) {
+      if (multi) return fail(MRBO_ERR_ARG, "gp_fit_multi: bad surrogate %d (d=%d N=%d)", q, s[q].d, s[q].N);
+      return fail(MRBO_ERR_ARG, "bad surrogate (d=%d N=%d)", d, N);
+    }
+    if (s[q].d != d || s[q].N != N || s[q].kernel != s->kernel || s[q].sigma_n2 != s->sigma_n2)
+      return fail(MRBO_ERR_ARG, "gp_fit_multi: surrogate %d differs from surrogate 0 in d, N, kernel or sigma_n2", q);
+  }
   if (N > 512) return fail(MRBO_ERR_UNSUPPORTED, "N=%d > 512", N);
   if (s->kernel < 0 || s->kernel > 4) return fail(MRBO_ERR_UNSUPPORTED, "gp_fit: kernel id %d", s->kernel);
   // θ = (ℓ) for the one-parameter kernels; Periodic takes (ℓ) (period fixed at s->period) or (ℓ, p)
   if (nt < 1 || nt > (s->kernel == 4 ? 2 : 1)) return fail(MRBO_ERR_ARG, "gp_fit: nt=%d for kernel %d", nt, s->kernel);
-  if (s->kernel == 4 && nt == 1 && !(s->period > 0.0)) return fail(MRBO_ERR_ARG, "gp_fit: period %g", s->period);
+  if (s->kernel == 4 && nt == 1)
+    for (int q = 0; q < ns; ++q)
+      if (!(s[q].period > 0.0)) return fail(MRBO_ERR_ARG, "gp_fit: period %g", s[q].period);
+  if (ns > 65535) return fail(MRBO_ERR_UNSUPPORTED, "gp_fit_multi: S=%d > 65535 (the grid's second dimension)", ns);
   hipStream_t st = (hipStream_t)stream;
-  const size_t P = (size_t)np, NN = (size_t)N * N, NTP = (size_t)nt * P;
+  const size_t S = (size_t)ns, PS = (size_t)np * S, NN = (size_t)N * N, NTP = (size_t)nt * PS, DN = (size_t)d * N;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
   Stage sg;
-  // inputs [θ (host calls) | X | y] packed into one pinned buffer and one host→device copy; the
-  // small outputs of host calls [ll | grad | status] in one device block and one copy back
-  const size_t n_th = host ? NTP : 0, n_in = n_th + (size_t)d * N + N;
-  const size_t out_bytes = sizeof(double) * (P + NTP) + sizeof(int32_t) * P;
+  // inputs [θ (host calls) | X | y | period], S blocks each, packed into one pinned buffer and one
+  // host→device copy; the small outputs of host calls [ll | grad | status] in one device block and
+  // one copy back
+  const size_t n_th = host ? NTP : 0, n_in = n_th + DN * S + N * S + S;
+  const size_t out_bytes = sizeof(double) * (PS + NTP) + sizeof(int32_t) * PS;
   double* din = (double*)sg.slot(sizeof(double) * n_in);
   if (!din) return fail(MRBO_ERR_NOMEM, "staging the inputs");
   const double* dth = host ? din : thetas;
   const double* dX = din + n_th;
-  const double* dy = dX + (size_t)d * N;
+  const double* dy = dX + DN * S;
+  const double* dper = dy + (size_t)N * S;
   double *dll_ = ll, *dgr = grad, *dL = L_out, *dc = c_out;
   int32_t* dst = status;
   if (host) {
     char* dout = (char*)sg.slot(out_bytes);
-    if (!dout || sg.out(NN * P, L_out, &dL) || sg.out((size_t)N * P, c_out, &dc))
+    if (!dout || sg.out(NN * PS, L_out, &dL) || sg.out((size_t)N * PS, c_out, &dc))
       return fail(MRBO_ERR_NOMEM, "staging allocation failed");
     dll_ = (double*)dout;
-    dgr = dll_ + P;
+    dgr = dll_ + PS;
     dst = (int32_t*)(dgr + NTP);
   }
-  GpFitParams q{d, N, s->kernel, s->sigma_n2, dX, dy, nt, dth, s->period, dll_, dgr, (int*)dst, dL, dc, nullptr};
+  GpFitParams q{d, N, s->kernel, s->sigma_n2, dX, dy, nt, dth, dper, dll_, dgr, (int*)dst, dL, dc, nullptr};
   {
     int dev = 0, lds_max = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -1410,7 +1426,7 @@ int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const d
                   need, lds_max);
   }
   if (!gpfit_in_regs(q) && !gpfit_in_lds(q)) {   // the register (N ≤ 64) and LDS (N ≤ 80) kernels need none
-    q.work = (double*)sg.slot(sizeof(double) * gpfit_tile_work_doubles(N, nt) * P);
+    q.work = (double*)sg.slot(sizeof(double) * gpfit_tile_work_doubles(N, nt) * PS);
     if (!q.work) return fail(MRBO_ERR_NOMEM, "gp_fit workspace");
   }
   Pinned pin_in(sizeof(double) * n_in), pin_out(host ? out_bytes : 0);
@@ -1418,8 +1434,12 @@ int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const d
   {
     double* h = (double*)pin_in.p;
     if (host) std::memcpy(h, thetas, sizeof(double) * NTP);
-    std::memcpy(h + n_th, s->X, sizeof(double) * d * N);
-    std::memcpy(h + n_th + (size_t)d * N, s->y, sizeof(double) * N);
+    double *hX = h + n_th, *hy = hX + DN * S, *hp = hy + (size_t)N * S;
+    for (size_t k = 0; k < S; ++k) {
+      std::memcpy(hX + DN * k, s[k].X, sizeof(double) * DN);
+      std::memcpy(hy + (size_t)N * k, s[k].y, sizeof(double) * N);
+      hp[k] = s[k].period;
+    }
   }
   // timing events per device (an event records only on streams of the device it was created on)
   static std::mutex gev_m;
@@ -1453,7 +1473,7 @@ int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const d
     if (hipStreamSynchronize(st) != hipSuccess) { sg.abandon(); pin_in.abandon(); }
     return fail(MRBO_ERR_HIP, "gp_fit: hipEventRecord: %s", hipGetErrorString(e));
   }
-  launch_gpfit(np, st, q);
+  launch_gpfit(np, ns, st, q);
   // the staging buffers and the workspace go back to the pool on return: once the launch is
   // issued, every path synchronises the stream first (an error after the launch must not hand
   // memory a running kernel still uses to another call), and keeps them out of the pool when
@@ -1479,13 +1499,23 @@ int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const d
   }
   if (host) {
     const double* h = (const double*)pin_out.p;
-    std::memcpy(ll, h, sizeof(double) * P);
-    std::memcpy(grad, h + P, sizeof(double) * NTP);
-    std::memcpy(status, h + P + NTP, sizeof(int32_t) * P);
-    if (L_out) HIP_TRY(hipMemcpy(L_out, dL, sizeof(double) * NN * P, hipMemcpyDeviceToHost));
-    if (c_out) HIP_TRY(hipMemcpy(c_out, dc, sizeof(double) * N * P, hipMemcpyDeviceToHost));
+    std::memcpy(ll, h, sizeof(double) * PS);
+    std::memcpy(grad, h + PS, sizeof(double) * NTP);
+    std::memcpy(status, h + PS + NTP, sizeof(int32_t) * PS);
+    if (L_out) HIP_TRY(hipMemcpy(L_out, dL, sizeof(double) * NN * PS, hipMemcpyDeviceToHost));
+    if (c_out) HIP_TRY(hipMemcpy(c_out, dc, sizeof(double) * N * PS, hipMemcpyDeviceToHost));
   }
   return MRBO_OK;
+}
+
+int mrbo_gp_fit_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas, double* ll,
+                      double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
+  return gp_fit_impl(s, S, P, nt, thetas, ll, grad, status, L_out, c_out, flags, stream, true);
+}
+
+int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const double* thetas, double* ll,
+                      double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
+  return gp_fit_impl(s, 1, np, nt, thetas, ll, grad, status, L_out, c_out, flags, stream, false);
 }
 
 int mrbo_gp_fit(const mrbo_surrogate_t* s, int32_t np, const double* ells, double* ll, double* dll, int32_t* status,

@@ -66,28 +66,32 @@ MRBO_DECLARE_DF4(5) MRBO_DECLARE_DF4(6) MRBO_DECLARE_DF4(7) MRBO_DECLARE_DF4(8)
 constexpr int F4_HMAX = 3;   // horizons served by the FMAX = 4 units
 constexpr int F4_DMAX = 8;
 
-// base-GP fit + marginal likelihood for P lengthscales (mrbo_gpfit.hip)
+// base-GP fit + marginal likelihood for P hyperparameter vectors on each of S data sets
+// (mrbo_gpfit.hip; mrbo_gp_fit_theta is S = 1).  The data sets share d, N, kernel and σn2; every
+// array holds S blocks, the data set index slowest, and workgroup (p, s) of the (P, S) grid takes
+// block s of each.
 struct GpFitParams {
   int d, N, kernel;
   double sn2;
-  const double* X;       // d×N
-  const double* y;       // N
+  const double* X;       // d×N×S
+  const double* y;       // N×S
   int nt;                // hyperparameters per candidate: 1 (ℓ) or 2 (ℓ, p: Periodic)
-  const double* thetas;  // nt×P
-  double period;         // Periodic with nt = 1: the surrogate's period
-  double* ll;            // P
-  double* grad;          // nt×P: ∂ll/∂θ_t
-  int* status;           // P: 0, or 1 = PosDefException
-  double* L_out;         // optional N×N×P
-  double* c_out;         // optional N×P
-  double* work;          // gpfit_tile_work_doubles(N, nt)·P (the tile kernel only)
+  const double* thetas;  // nt×P×S
+  const double* periods; // S.  Periodic with nt = 1: the data sets' periods
+  double* ll;            // P×S
+  double* grad;          // nt×P×S: ∂ll/∂θ_t
+  int* status;           // P×S: 0, or 1 = PosDefException
+  double* L_out;         // optional N×N×P×S
+  double* c_out;         // optional N×P×S
+  double* work;          // gpfit_tile_work_doubles(N, nt)·P·S (the tile kernel only)
 };
 // MRBO_GPFIT_LDS_MAX < N ≤ 512: gpfit_tile_kernel's workspace per candidate
 size_t gpfit_tile_work_doubles(int N, int nt);
 // LDS bytes per workgroup of the kernel launch_gpfit selects for q (the tile kernel stages X:
 // d·⌈N/32⌉·32 doubles, so large d can exceed the CU's 160 KB)
 size_t gpfit_launch_lds(const GpFitParams& q);
-void launch_gpfit(int P, hipStream_t st, const GpFitParams& q);
+// one launch, grid (P, S)
+void launch_gpfit(int P, int S, hipStream_t st, const GpFitParams& q);
 // 32 < N ≤ 64, d ≤ 16 and no factor / coefficient outputs: the one-wave-per-candidate register
 // kernel (no workspace).  N ≤ 32 is one tile of the tile kernel: its register factor and inverse
 // of a 32 × 32 tile do a quarter of the 64-row kernel's work (N = 32: 0.045 ms per 256 candidates

@@ -23,6 +23,11 @@
 // everything in LDS; it holds candidates up to N = 128, but the tile kernel is faster above 80).
 // 80 < N ≤ 512: gpfit_tile_kernel (below): one workgroup per candidate, the blocked algorithm on
 // 32 × 32 tiles in a global workspace with the tile products on the fp64 matrix cores.
+//
+// mrbo_gp_fit_multi (no reference counterpart): S data sets of one d, N, kernel and σn2 with P
+// candidates each in ONE launch of grid (P, S): see gpfit_candidate below.  The arithmetic of a fit is
+// untouched, so block s of the outputs carries the bits of a launch on data set s alone;
+// mrbo_gp_fit_theta is the S = 1 launch.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -94,11 +99,21 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return r;
 }
 
+// Workgroup (blockIdx.x, blockIdx.y = s) of the (P, S) grid fits candidate blockIdx.x of data set s.
+// Every array holds S blocks with the data set index slowest, so everything that is indexed by
+// candidate -- θ, ll, grad, status, L_out, c_out, the tile workspace -- is addressed by the GLOBAL
+// candidate index p = blockIdx.x + s·P exactly as a one-data-set launch addresses candidate p, and
+// the kernels' pointers stay plain kernel arguments (re-loadable from the kernarg segment wherever
+// they are used; a pointer offset per workgroup would be one more 64-bit scalar held or spilled
+// across each kernel).  Only X, y and the period are per data set: X and y are
+// read at the element offsets s·d·N and s·N, the period at periods[s].
+__device__ __forceinline__ int gpfit_candidate(int P) { return blockIdx.x + blockIdx.y * P; }
+
 // candidate p's hyperparameters: θ_p = thetas[p·nt .. p·nt + nt − 1] = (ℓ[, p]); with nt = 1 the
-// Periodic kernel keeps the surrogate's period
+// Periodic kernel keeps the data set's period
 __device__ __forceinline__ void cand_theta(const GpFitParams& q, int p, double& ell, double& per) {
   ell = q.thetas[(size_t)p * q.nt];
-  per = (q.nt > 1) ? q.thetas[(size_t)p * q.nt + 1] : q.period;
+  per = (q.nt > 1) ? q.thetas[(size_t)p * q.nt + 1] : q.periods[blockIdx.y];
 }
 
 // ---- N ≤ 64: one wave per candidate, K rows in registers --------------------------------
@@ -290,8 +305,9 @@ constexpr int GR_WAVES = 4;
 template <int NT>
 __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q, int P) {
   extern __shared__ __attribute__((aligned(16))) double gsm[];
-  const int p = blockIdx.x, lane = threadIdx.x & 63, tid = threadIdx.x;
-  if (p >= P) return;   // whole workgroups
+  const int lane = threadIdx.x & 63, tid = threadIdx.x;
+  if ((int)blockIdx.x >= P) return;   // whole workgroups
+  const int p = gpfit_candidate(P);
 #ifdef MRBO_GPFIT_STAMPS
   unsigned long long gr_ts[6], gr_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -301,11 +317,12 @@ __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q,
   double* XS = cs + 64;                 // X[u][j] at u·64 + j (u < d)
   double* VS = XS + 16 * 64;            // V = L⁻¹, row-major (m·LD + j)
   const int N = q.N, d = q.d;
+  const size_t xo = (size_t)blockIdx.y * d * N, yo = (size_t)blockIdx.y * N;   // this data set's X and y
   const bool act = lane < N;
   double ell, per;
   cand_theta(q, p, ell, per);
   if (tid < 64)
-    for (int u = 0; u < d; ++u) XS[u * 64 + lane] = act ? q.X[u + d * lane] : 0.0;
+    for (int u = 0; u < d; ++u) XS[u * 64 + lane] = act ? q.X[xo + u + d * lane] : 0.0;
   __syncthreads();
   GR_STAMP(0);
   // K (eval_KXX :161-178, ψ(0) + σn2 on the diagonal; padding = identity) and δK_t (eval_Dθ_KXX
@@ -391,11 +408,11 @@ __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q,
   if (w == 0) {
     // c = L'\(L\y), column-oriented substitutions (ck broadcast by readlane)
     const double rdg = 1.0 / dg;
-    double c = act ? q.y[lane] : 0.0;
+    double c = act ? q.y[yo + lane] : 0.0;
     gr_solve(c, a, LV, rdg, lane, N, std::make_integer_sequence<int, 64>{});
     GR_STAMP(3);
     cs[lane] = c;
-    const double yc = gr_sum(act ? q.y[lane] * c : 0.0);
+    const double yc = gr_sum(act ? q.y[yo + lane] * c : 0.0);
     if (lane == 0) part[0][2 * NT] = yc;
   } else if (w == 1) {
     // V = L⁻¹ by columns (lane j = column j), rows ascending (rows ≥ N: identity, no effect on
@@ -494,8 +511,9 @@ __global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, in
   double* cv = dv + GL_N;               // y, then c
   __shared__ double part[GL_THREADS / 64][2 * NT + 2];
   __shared__ int fail;
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (p >= P) return;   // whole workgroups
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if ((int)blockIdx.x >= P) return;   // whole workgroups
+  const int p = gpfit_candidate(P);
 #ifdef MRBO_GPFIT_STAMPS
   unsigned long long gl_ts[6], gl_t0 = __builtin_amdgcn_s_memtime();
 #define GL_STAMP(k) gl_ts[k] = __builtin_amdgcn_s_memtime()
@@ -503,14 +521,15 @@ __global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, in
 #define GL_STAMP(k) ((void)0)
 #endif
   const int N = q.N, d = q.d;
+  const size_t xo = (size_t)blockIdx.y * d * N, yo = (size_t)blockIdx.y * N;   // this data set's X and y
   double ell, per;
   cand_theta(q, p, ell, per);
   if (tid == 0) fail = 0;
   for (int idx = tid; idx < d * N; idx += GL_THREADS) {
     const int u = idx % d, i = idx / d;
-    XS[u * GL_N + i] = q.X[idx];
+    XS[u * GL_N + i] = q.X[xo + idx];
   }
-  for (int i = tid; i < N; i += GL_THREADS) cv[i] = q.y[i];
+  for (int i = tid; i < N; i += GL_THREADS) cv[i] = q.y[yo + i];
   __syncthreads();
   // K (eval_KXX :161-178, ψ(0) + σn2 on the diagonal) over the pairs j ≤ i, lower triangle
   const int npair = N * (N + 1) / 2;
@@ -629,7 +648,7 @@ __global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, in
     for (int s2 = 0; s2 < 2; ++s2) {
       const int i = lane + 64 * s2;
       if (i < N) {
-        yc = fma(q.y[i], r[s2], yc);
+        yc = fma(q.y[yo + i], r[s2], yc);
         lg += log(ld_[i]);
       }
     }
@@ -871,12 +890,14 @@ __device__ __forceinline__ void tt_panel(double (&v)[TT], const double* Dk, cons
 template <int NT>
 __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, int P) {
   extern __shared__ __attribute__((aligned(16))) double tsm[];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (p >= P) return;   // whole workgroups
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if ((int)blockIdx.x >= P) return;   // whole workgroups
+  const int p = gpfit_candidate(P);
 #ifdef MRBO_GPFIT_STAMPS
   unsigned long long tt_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tt_last = __builtin_amdgcn_s_memtime();
 #endif
   const int N = q.N, d = q.d, T = (N + TT - 1) / TT, NP = T * TT;
+  const size_t xo = (size_t)blockIdx.y * d * N, yo = (size_t)blockIdx.y * N;   // this data set's X and y
   double* XS = tsm;                      // X[u][i] at u·NP + i, zero-padded
   double* Dk = XS + (size_t)d * NP;      // diagonal tile A_kk → L_kk, 32 × 33 column-major
   double* Wk = Dk + TT * TT_LD;          // W_k = L_kk⁻¹, 32 × 33 column-major
@@ -887,9 +908,9 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
   double* rdall = uv + NP;               // 1/L_ii of every row (the substitutions multiply)
   __shared__ double part[TT_THREADS / 64][2 * NT + 2];
   __shared__ int fail;
+  const size_t ntile = (size_t)T * (T + 1) / 2;
   double ell, per;
   cand_theta(q, p, ell, per);
-  const size_t ntile = (size_t)T * (T + 1) / 2;
   double* Lt = q.work + (size_t)p * ((2 + NT) * ntile + T) * (TT * TT);
   double* Vt = Lt + ntile * (TT * TT);
   double* Wt = Vt + ntile * (TT * TT);
@@ -897,9 +918,9 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
   if (tid == 0) fail = 0;
   for (int idx = tid; idx < d * NP; idx += TT_THREADS) {
     const int u = idx / NP, i = idx % NP;
-    XS[idx] = (i < N) ? q.X[u + (size_t)d * i] : 0.0;
+    XS[idx] = (i < N) ? q.X[xo + u + (size_t)d * i] : 0.0;
   }
-  for (int i = tid; i < NP; i += TT_THREADS) yv[i] = (i < N) ? q.y[i] : 0.0;
+  for (int i = tid; i < NP; i += TT_THREADS) yv[i] = (i < N) ? q.y[yo + i] : 0.0;
   __syncthreads();
   // K (eval_KXX :161-178, ψ(0) + σn2 on the diagonal), every entry of the lower tiles
   // (tile by tile: the tile's (I, J) once per tile instead of a square root per entry; the
@@ -1187,7 +1208,7 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
       }
       gr_sync();
       if (lane < TT) {
-        if (TT * I + i < N) yc = fma(q.y[TT * I + i], r, yc);
+        if (TT * I + i < N) yc = fma(q.y[yo + TT * I + i], r, yc);
         yv[TT * I + i] = r;   // c (y_I is no longer needed: rows > I are done)
       }
       gr_sync();
@@ -1302,25 +1323,25 @@ size_t gpfit_launch_lds(const GpFitParams& q) {
   return dyn;
 }
 
-void launch_gpfit(int P, hipStream_t st, const GpFitParams& q) {
+void launch_gpfit(int P, int S, hipStream_t st, const GpFitParams& q) {
   if (gpfit_in_regs(q)) {
     if (q.nt == 2)
-      hipLaunchKernelGGL(gpfit_reg_kernel<2>, dim3(P), dim3(64 * GR_WAVES), gpfit_reg_lds(2), st, q, P);
+      hipLaunchKernelGGL(gpfit_reg_kernel<2>, dim3(P, S), dim3(64 * GR_WAVES), gpfit_reg_lds(2), st, q, P);
     else
-      hipLaunchKernelGGL(gpfit_reg_kernel<1>, dim3(P), dim3(64 * GR_WAVES), gpfit_reg_lds(1), st, q, P);
+      hipLaunchKernelGGL(gpfit_reg_kernel<1>, dim3(P, S), dim3(64 * GR_WAVES), gpfit_reg_lds(1), st, q, P);
     return;
   }
   if (gpfit_in_lds(q)) {
     if (q.nt == 2)
-      hipLaunchKernelGGL(gpfit_lds_kernel<2>, dim3(P), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
+      hipLaunchKernelGGL(gpfit_lds_kernel<2>, dim3(P, S), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
     else
-      hipLaunchKernelGGL(gpfit_lds_kernel<1>, dim3(P), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
+      hipLaunchKernelGGL(gpfit_lds_kernel<1>, dim3(P, S), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
     return;
   }
   if (q.nt == 2)
-    hipLaunchKernelGGL(gpfit_tile_kernel<2>, dim3(P), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
+    hipLaunchKernelGGL(gpfit_tile_kernel<2>, dim3(P, S), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
   else
-    hipLaunchKernelGGL(gpfit_tile_kernel<1>, dim3(P), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
+    hipLaunchKernelGGL(gpfit_tile_kernel<1>, dim3(P, S), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
 }
 
 }  // namespace mrbo

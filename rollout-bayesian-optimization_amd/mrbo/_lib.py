@@ -36,7 +36,7 @@ EXPORTS = [
     "mrbo_initial_guesses", "mrbo_dual_uniform", "mrbo_last_kernel_ms", "mrbo_gp_fit", "mrbo_gp_fit_theta",
     "mrbo_plan_info", "mrbo_last_gp_fit_ms", "mrbo_plan_set_order", "mrbo_base_solve", "mrbo_sga_step",
     "mrbo_kernel_times", "mrbo_merge_moments", "mrbo_adam_step", "mrbo_stochastic_solve",
-    "mrbo_plan_order_longest_first", "mrbo_plan_create_batch",
+    "mrbo_plan_order_longest_first", "mrbo_plan_create_batch", "mrbo_gp_fit_multi",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM = 0, 1
@@ -114,6 +114,8 @@ def load():
                               ctypes.c_uint32, _vp]
     L.mrbo_gp_fit_theta.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
                                     _vp, _vp, _vp, ctypes.c_uint32, _vp]
+    L.mrbo_gp_fit_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
     L.mrbo_last_kernel_ms.argtypes = [_vp]
     L.mrbo_last_kernel_ms.restype = ctypes.c_double
     L.mrbo_plan_info.argtypes = [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]

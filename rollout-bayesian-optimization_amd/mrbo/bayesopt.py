@@ -258,6 +258,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
             ell_starts = [float(s.ψ.lengthscale) for s in surs]
             initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
             rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
+            mle_times = np.zeros(budget)   # wall time of the chunk's batched refit per budget step
             for b in range(budget):
                 t0 = time.perf_counter()
                 picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
@@ -269,16 +270,18 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                     r["simple_regret"][b] = simple_regret(true_minimum, observed_best)
                     r["gaps"][b] = gap(initial_best, observed_best, true_minimum)
                     s.condition(xnext, float(testfn.f(xnext)))
-                    if optimize:
-                        from .mle import optimize as mle_optimize
-                        mle_optimize(s, KERNEL_LBS, KERNEL_UBS)
                     r["minimum_observations"][b] = float(np.min(s.get_active_observations()))
+                if optimize:   # every trial has conditioned: one batched refit for the chunk
+                    from .mle import optimize_multi
+                    t0 = time.perf_counter()
+                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS)
+                    mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start in zip(chunk, surs, rec, ell_starts):
                 log(f"{acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, {r['times'].sum():.2f} s of solves")
                 for metric in METRICS:
                     write_to_csv(os.path.join(directory, f"{acq}_{metric}"), r[metric])
                 results[(acq, trial)] = dict(times=r["times"], gaps=r["gaps"], simple_regret=r["simple_regret"],
-                                             minimum_observations=r["minimum_observations"],
+                                             minimum_observations=r["minimum_observations"], mle_times=mle_times.copy(),
                                              X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
                                              ell_start=ell_start, ell_end=float(s.ψ.lengthscale),
                                              repeats=np.zeros(budget, dtype=bool))
@@ -383,6 +386,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
             rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
             reps = [np.zeros(budget, dtype=bool) for _ in chunk]
+            mle_times = np.zeros(budget)   # wall time of the chunk's batched refit per budget step
             tol = 1e-6 * (ubs - lbs)[:, None]
             for b in range(budget):
                 t0 = time.perf_counter()
@@ -402,17 +406,19 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                     r["simple_regret"][b] = simple_regret(true_minimum, observed_best)
                     r["gaps"][b] = gap(initial_best, observed_best, true_minimum)
                     s.condition(xnext, float(testfn.f(xnext)))
-                    if optimize:
-                        from .mle import optimize as mle_optimize
-                        mle_optimize(s, KERNEL_LBS, KERNEL_UBS)
                     r["minimum_observations"][b] = float(np.min(s.get_active_observations()))
+                if optimize:   # every trial has conditioned: one batched refit for the chunk
+                    from .mle import optimize_multi
+                    t0 = time.perf_counter()
+                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS)
+                    mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start, rp in zip(chunk, surs, rec, ell_starts, reps):
                 log(f"myopic {acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, "
                     f"{r['times'].sum():.2f} s of solves")
                 for metric in METRICS:
                     write_to_csv(os.path.join(directory, f"{acq}_{metric}"), r[metric])
                 results[(acq, trial)] = dict(times=r["times"], gaps=r["gaps"], simple_regret=r["simple_regret"],
-                                             minimum_observations=r["minimum_observations"],
+                                             minimum_observations=r["minimum_observations"], mle_times=mle_times.copy(),
                                              X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
                                              ell_start=ell_start, ell_end=float(s.ψ.lengthscale), repeats=rp)
         for trial in range(trials if parallel_trials == 1 else 0):
