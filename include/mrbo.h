@@ -345,6 +345,40 @@ int mrbo_gp_fit(const mrbo_surrogate_t* s, int32_t P, const double* ells, double
 int mrbo_gp_fit_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas, double* ll,
                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream);
 
+/* optimize!(s; lowerbounds, upperbounds, optim_options) r_b_s.jl:805-829 for S data sets in ONE
+ * call: S independent minimisations of −log_likelihood over the box [lower, upper], problem q from
+ * theta0[q·nt ..] on data set s[q], by the build's projected L-BFGS with a batched backtracking line
+ * search (mrbo/mle.py lbfgs_scalar is its specification, operation for operation).  The data sets
+ * are staged once; one fit launch of grid (1, S) evaluates the clipped starts, then every round is
+ * one fit launch of grid (12, S) -- the trial steps 1, 1/2, ..., 2⁻¹¹ of every problem -- and one
+ * step kernel that accepts the line search, updates x, f, g and the (s, y) history and proposes the
+ * next 12 trial θ, all on the device and without a host round trip: at most iterations + 1 rounds,
+ * the start's included.  A stopped problem (converged, no Armijo step, zero move, budget spent)
+ * keeps its state and its trial θ (its clipped start, if it stopped before any line search); the host reads the number of running problems two rounds
+ * behind the launches, and the rounds launched after the last stop change no output.  A fit with
+ * status ≠ 0 counts as f = NaN (never accepted; a failing start stops its problem after one line
+ * search, with f = NaN at its clipped start).
+ *   theta0   nt×S starts;  lower, upper  nt box bounds (HOST memory, finite, lower ≤ upper)
+ *   opts     NULL: the defaults (a zero field takes its default)
+ *   theta    nt×S minimisers;  nll  S: −log_likelihood there;  grad  nt×S: its gradient
+ *   iters    S: line searches made (projected_lbfgs's iteration count)
+ *   result   HOST int32[2]: rounds launched, the round after which no problem ran (1 + max iters)
+ * theta0 / theta / nll / grad / iters are device pointers unless MRBO_FLAG_HOST_POINTERS.  The
+ * checks on s, S and nt are mrbo_gp_fit_multi's; MRBO_ERR_ARG, before any device call, also for
+ * lower > upper, a non-finite bound, history outside 1..16 (0: default), iterations < 0, a
+ * negative or non-finite g_tol or c1, a null array, a flag other than MRBO_FLAG_HOST_POINTERS.  Kernel selection, workspace and the LDS limit
+ * are those of a mrbo_gp_fit_multi call with P = 12.  Synchronises the stream once, at the end;
+ * mrbo_last_gp_fit_ms is left as it was. */
+typedef struct {
+  int32_t iterations;  /* line searches at most (Optim.Options(iterations=30)); 0 → 30 */
+  int32_t history;     /* L-BFGS pairs kept, 1..16; 0 → 10 */
+  double  g_tol;       /* 0 → 1e-8 */
+  double  c1;          /* Armijo constant; 0 → 1e-4 */
+} mrbo_mle_opts_t;
+int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t S, int32_t nt, const double* theta0,
+                           const double* lower, const double* upper, const mrbo_mle_opts_t* opts, double* theta,
+                           double* nll, double* grad, int32_t* iters, int32_t* result, uint32_t flags, void* stream);
+
 /* Host helpers (HOST memory). */
 int mrbo_rnstream(int32_t M, int32_t d, int32_t H, double* out);                 /* M×(d+1)×H */
 int mrbo_initial_guesses(int32_t n, int32_t d, const double* lbs, const double* ubs, double* out); /* d×(n+2) */

@@ -16,6 +16,7 @@
 #include "../../include/mrbo.h"
 #define MRBO_API_TU
 #include "mrbo_dispatch.h"
+#include "mrbo_mle.h"
 #include "sobol_table.h"
 
 namespace mrbo {   // mrbo_order.hip
@@ -1366,14 +1367,16 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   return MRBO_OK;
 }
 
-// mrbo_gp_fit_multi and, as its S = 1 case, mrbo_gp_fit_theta (`multi` only words the messages)
-static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_t nt, const double* thetas, double* ll,
-                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream,
-                       bool multi) {
-  if (!s || !thetas || !ll || !grad || !status || np < 1) return fail(MRBO_ERR_ARG, "null argument");
+// ---- the GP fit entry points ---------------------------------------------------------------
+// A fit call is three parts: gp_fit_stage (the data sets to the device, one copy), gp_fit_launch
+// (one launch, no synchronisation) and gp_fit_copy_back (a host call's small outputs).  The plain
+// calls (gp_fit_impl) run them once around one synchronisation; mrbo_gp_optimize_multi stages
+// once and launches every round of its minimisation.
+
+// the argument checks on s, S and nt, before the first HIP call (`multi` only words the messages)
+static int gp_fit_check(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, bool multi) {
   if (ns < 1) return fail(MRBO_ERR_ARG, "gp_fit_multi: S=%d", ns);
   const int d = s->d, N = s->N;
-  // every argument check comes before the first HIP call
   for (int q = 0; q < ns; ++q) {
     if (s[q].d < 1 || s[q].N < 1 || !s[q].X || !s[q].y) {
       if (multi) return fail(MRBO_ERR_ARG, "gp_fit_multi: bad surrogate %d (d=%d N=%d)", q, s[q].d, s[q].N);
@@ -1390,32 +1393,47 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
     for (int q = 0; q < ns; ++q)
       if (!(s[q].period > 0.0)) return fail(MRBO_ERR_ARG, "gp_fit: period %g", s[q].period);
   if (ns > 65535) return fail(MRBO_ERR_UNSUPPORTED, "gp_fit_multi: S=%d > 65535 (the grid's second dimension)", ns);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t S = (size_t)ns, PS = (size_t)np * S, NN = (size_t)N * N, NTP = (size_t)nt * PS, DN = (size_t)d * N;
-  const bool host = flags & MRBO_FLAG_HOST_POINTERS;
+  return MRBO_OK;
+}
+
+// the staged inputs of one call: [θ (n_th doubles, or none) | X | y | period], S blocks each, packed
+// into one pinned buffer and one host→device copy, and the device buffers of the call (back to
+// the pool when it returns)
+struct GpFitStaged {
   Stage sg;
-  // inputs [θ (host calls) | X | y | period], S blocks each, packed into one pinned buffer and one
-  // host→device copy; the small outputs of host calls [ll | grad | status] in one device block and
-  // one copy back
-  const size_t n_th = host ? NTP : 0, n_in = n_th + DN * S + N * S + S;
-  const size_t out_bytes = sizeof(double) * (PS + NTP) + sizeof(int32_t) * PS;
-  double* din = (double*)sg.slot(sizeof(double) * n_in);
-  if (!din) return fail(MRBO_ERR_NOMEM, "staging the inputs");
-  const double* dth = host ? din : thetas;
-  const double* dX = din + n_th;
-  const double* dy = dX + DN * S;
-  const double* dper = dy + (size_t)N * S;
-  double *dll_ = ll, *dgr = grad, *dL = L_out, *dc = c_out;
-  int32_t* dst = status;
-  if (host) {
-    char* dout = (char*)sg.slot(out_bytes);
-    if (!dout || sg.out(NN * PS, L_out, &dL) || sg.out((size_t)N * PS, c_out, &dc))
-      return fail(MRBO_ERR_NOMEM, "staging allocation failed");
-    dll_ = (double*)dout;
-    dgr = dll_ + PS;
-    dst = (int32_t*)(dgr + NTP);
+  Pinned pin_in;
+  size_t n_th, n_in;
+  GpFitParams q{};   // the caller sets the outputs (L_out, c_out before gp_fit_stage: they select the kernel)
+  GpFitStaged(size_t n_theta, size_t n_data) : pin_in(sizeof(double) * (n_theta + n_data)), n_th(n_theta), n_in(n_theta + n_data) {}
+  // after an error: the buffers go back to the pool only when the stream has drained (a copy or
+  // a kernel may still use them)
+  void drain(hipStream_t st) {
+    if (hipStreamSynchronize(st) != hipSuccess) {
+      sg.abandon();
+      pin_in.abandon();
+    }
   }
-  GpFitParams q{d, N, s->kernel, s->sigma_n2, dX, dy, nt, dth, dper, dll_, dgr, (int*)dst, dL, dc, nullptr};
+};
+
+// S data sets (and `thetas`, n_th host doubles) to the device on `st`; fills f.q except its outputs
+// and, without staged θ, its thetas.  ncand: candidates of the largest launch (P·S), which sizes
+// the tile kernel's workspace.  Once the copy is issued every error path drains the stream first.
+static int gp_fit_stage(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const double* thetas, size_t ncand,
+                        hipStream_t st, GpFitStaged& f) {
+  const int d = s->d, N = s->N;
+  const size_t S = (size_t)ns, DN = (size_t)d * N;
+  double* din = (double*)f.sg.slot(sizeof(double) * f.n_in);
+  if (!din) return fail(MRBO_ERR_NOMEM, "staging the inputs");
+  GpFitParams& q = f.q;
+  q.d = d;
+  q.N = N;
+  q.kernel = s->kernel;
+  q.sn2 = s->sigma_n2;
+  q.nt = nt;
+  if (f.n_th) q.thetas = din;
+  q.X = din + f.n_th;
+  q.y = q.X + DN * S;
+  q.periods = q.y + (size_t)N * S;
   {
     int dev = 0, lds_max = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -1426,21 +1444,79 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
                   need, lds_max);
   }
   if (!gpfit_in_regs(q) && !gpfit_in_lds(q)) {   // the register (N ≤ 64) and LDS (N ≤ 80) kernels need none
-    q.work = (double*)sg.slot(sizeof(double) * gpfit_tile_work_doubles(N, nt) * PS);
+    q.work = (double*)f.sg.slot(sizeof(double) * gpfit_tile_work_doubles(N, nt) * ncand);
     if (!q.work) return fail(MRBO_ERR_NOMEM, "gp_fit workspace");
   }
-  Pinned pin_in(sizeof(double) * n_in), pin_out(host ? out_bytes : 0);
-  if (!pin_in.p || (host && !pin_out.p)) return fail(MRBO_ERR_NOMEM, "pinned staging");
+  if (!f.pin_in.p) return fail(MRBO_ERR_NOMEM, "pinned staging");
   {
-    double* h = (double*)pin_in.p;
-    if (host) std::memcpy(h, thetas, sizeof(double) * NTP);
-    double *hX = h + n_th, *hy = hX + DN * S, *hp = hy + (size_t)N * S;
+    double* h = (double*)f.pin_in.p;
+    if (f.n_th) std::memcpy(h, thetas, sizeof(double) * f.n_th);
+    double *hX = h + f.n_th, *hy = hX + DN * S, *hp = hy + (size_t)N * S;
     for (size_t k = 0; k < S; ++k) {
       std::memcpy(hX + DN * k, s[k].X, sizeof(double) * DN);
       std::memcpy(hy + (size_t)N * k, s[k].y, sizeof(double) * N);
       hp[k] = s[k].period;
     }
   }
+  const hipError_t e = hipMemcpyAsync(din, f.pin_in.p, sizeof(double) * f.n_in, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    f.drain(st);
+    return fail(MRBO_ERR_HIP, "gp_fit: staging copy: %s", hipGetErrorString(e));
+  }
+  return MRBO_OK;
+}
+
+// one launch of grid (P, S) on `st`, not synchronised
+static hipError_t gp_fit_launch(int P, int S, hipStream_t st, const GpFitParams& q) {
+  launch_gpfit(P, S, st, q);
+  return hipGetLastError();
+}
+
+// the outputs of a host call, after the stream has synchronised: [ll | grad | status] from the
+// pinned block `h`, the factors and coefficients straight from the device
+static int gp_fit_copy_back(const GpFitParams& q, const void* h_, size_t PS, size_t N, double* ll, double* grad,
+                            int32_t* status, double* L_out, double* c_out) {
+  const double* h = (const double*)h_;
+  const size_t NTP = (size_t)q.nt * PS;
+  std::memcpy(ll, h, sizeof(double) * PS);
+  std::memcpy(grad, h + PS, sizeof(double) * NTP);
+  std::memcpy(status, h + PS + NTP, sizeof(int32_t) * PS);
+  if (L_out) HIP_TRY(hipMemcpy(L_out, q.L_out, sizeof(double) * N * N * PS, hipMemcpyDeviceToHost));
+  if (c_out) HIP_TRY(hipMemcpy(c_out, q.c_out, sizeof(double) * N * PS, hipMemcpyDeviceToHost));
+  return MRBO_OK;
+}
+
+// mrbo_gp_fit_multi and, as its S = 1 case, mrbo_gp_fit_theta
+static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_t nt, const double* thetas, double* ll,
+                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream,
+                       bool multi) {
+  if (!s || !thetas || !ll || !grad || !status || np < 1) return fail(MRBO_ERR_ARG, "null argument");
+  if (const int rc = gp_fit_check(s, ns, nt, multi)) return rc;
+  const int d = s->d, N = s->N;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t S = (size_t)ns, PS = (size_t)np * S, NN = (size_t)N * N, NTP = (size_t)nt * PS, DN = (size_t)d * N;
+  const bool host = flags & MRBO_FLAG_HOST_POINTERS;
+  // θ of a host call travels with the data sets; its small outputs [ll | grad | status] share one
+  // device block and one copy back
+  GpFitStaged f(host ? NTP : 0, DN * S + N * S + S);
+  GpFitParams& q = f.q;
+  const size_t out_bytes = sizeof(double) * (PS + NTP) + sizeof(int32_t) * PS;
+  q.thetas = thetas;
+  q.ll = ll;
+  q.grad = grad;
+  q.status = (int*)status;
+  q.L_out = L_out;
+  q.c_out = c_out;
+  if (host) {
+    char* dout = (char*)f.sg.slot(out_bytes);
+    if (!dout || f.sg.out(NN * PS, L_out, &q.L_out) || f.sg.out((size_t)N * PS, c_out, &q.c_out))
+      return fail(MRBO_ERR_NOMEM, "staging allocation failed");
+    q.ll = (double*)dout;
+    q.grad = q.ll + PS;
+    q.status = (int*)(q.grad + NTP);
+  }
+  Pinned pin_out(host ? out_bytes : 0);
+  if (host && !pin_out.p) return fail(MRBO_ERR_NOMEM, "pinned staging");
   // timing events per device (an event records only on streams of the device it was created on)
   static std::mutex gev_m;
   static std::vector<std::pair<hipEvent_t, hipEvent_t>> gevs;
@@ -1461,33 +1537,26 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
     gev[0] = gevs[dev].first;
     gev[1] = gevs[dev].second;
   }
-  // from here on every return path synchronises the stream first (the copy reads pin_in)
-  {
-    const hipError_t e = hipMemcpyAsync(din, pin_in.p, sizeof(double) * n_in, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-      if (hipStreamSynchronize(st) != hipSuccess) { sg.abandon(); pin_in.abandon(); }
-      return fail(MRBO_ERR_HIP, "gp_fit: staging copy: %s", hipGetErrorString(e));
-    }
-  }
+  // from the staging copy on every return path synchronises the stream first (the copy reads pin_in)
+  if (const int rc = gp_fit_stage(s, ns, nt, thetas, PS, st, f)) return rc;
   if (const hipError_t e = hipEventRecord(gev[0], st); e != hipSuccess) {
-    if (hipStreamSynchronize(st) != hipSuccess) { sg.abandon(); pin_in.abandon(); }
+    f.drain(st);
     return fail(MRBO_ERR_HIP, "gp_fit: hipEventRecord: %s", hipGetErrorString(e));
   }
-  launch_gpfit(np, ns, st, q);
   // the staging buffers and the workspace go back to the pool on return: once the launch is
   // issued, every path synchronises the stream first (an error after the launch must not hand
   // memory a running kernel still uses to another call), and keeps them out of the pool when
   // even that fails
   {
-    hipError_t e = hipGetLastError();
+    hipError_t e = gp_fit_launch(np, ns, st, q);
     if (e == hipSuccess) e = hipEventRecord(gev[1], st);
     // the small outputs of a host call come back on the same stream (into pinned memory), so
     // one synchronisation covers the kernel and the copy
-    if (e == hipSuccess && host) e = hipMemcpyAsync(pin_out.p, dll_, out_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && host) e = hipMemcpyAsync(pin_out.p, q.ll, out_bytes, hipMemcpyDeviceToHost, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (es != hipSuccess) {
-      sg.abandon();
-      pin_in.abandon();
+      f.sg.abandon();
+      f.pin_in.abandon();
       pin_out.abandon();
       return fail(MRBO_ERR_HIP, "gp_fit: hipStreamSynchronize: %s", hipGetErrorString(es));
     }
@@ -1497,14 +1566,7 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
     float ms = -1.f;
     if (hipEventElapsedTime(&ms, gev[0], gev[1]) == hipSuccess) g_gpfit_ms = ms;
   }
-  if (host) {
-    const double* h = (const double*)pin_out.p;
-    std::memcpy(ll, h, sizeof(double) * PS);
-    std::memcpy(grad, h + PS, sizeof(double) * NTP);
-    std::memcpy(status, h + PS + NTP, sizeof(int32_t) * PS);
-    if (L_out) HIP_TRY(hipMemcpy(L_out, dL, sizeof(double) * NN * PS, hipMemcpyDeviceToHost));
-    if (c_out) HIP_TRY(hipMemcpy(c_out, dc, sizeof(double) * N * PS, hipMemcpyDeviceToHost));
-  }
+  if (host) return gp_fit_copy_back(q, pin_out.p, PS, (size_t)N, ll, grad, status, L_out, c_out);
   return MRBO_OK;
 }
 
@@ -1524,6 +1586,186 @@ int mrbo_gp_fit(const mrbo_surrogate_t* s, int32_t np, const double* ells, doubl
 }
 
 double mrbo_last_gp_fit_ms(void) { return g_gpfit_ms; }
+
+// The events of mrbo_gp_optimize_multi's check ring: a set per call in flight, pooled per device
+// like the buffers (an event records only on streams of the device it was created on).
+namespace {
+constexpr int MLE_NCHK = 8;
+struct CheckEvents {
+  int dev = 0;
+  hipEvent_t ev[MLE_NCHK] = {};
+  bool ok = false;
+  static std::mutex& mutex() { static std::mutex m; return m; }
+  static std::vector<CheckEvents>& pool() { static std::vector<CheckEvents> v; return v; }
+  void take() {
+    if (hipGetDevice(&dev) != hipSuccess) return;
+    {
+      std::lock_guard<std::mutex> lk(mutex());
+      auto& v = pool();
+      for (size_t i = 0; i < v.size(); ++i)
+        if (v[i].dev == dev) {
+          *this = v[i];
+          v.erase(v.begin() + i);
+          return;
+        }
+    }
+    for (auto& e : ev)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+        for (auto& x : ev)
+          if (x) (void)hipEventDestroy(x);
+        return;
+      }
+    ok = true;
+  }
+  void give() {
+    if (!ok) return;
+    std::lock_guard<std::mutex> lk(mutex());
+    pool().push_back(*this);
+    ok = false;
+  }
+};
+}  // namespace
+
+int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const double* theta0,
+                           const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
+                           double* nll, double* grad, int32_t* iters, int32_t* result, uint32_t flags, void* stream) {
+  // every argument check comes before the first HIP call
+  if (!s || !theta0 || !lower || !upper || !theta || !nll || !grad || !iters || !result)
+    return fail(MRBO_ERR_ARG, "gp_optimize_multi: null argument");
+  if (const int rc = gp_fit_check(s, ns, nt, true)) return rc;
+  MleParams mp{};
+  for (int t = 0; t < nt; ++t) {
+    if (!std::isfinite(lower[t]) || !std::isfinite(upper[t]) || lower[t] > upper[t])
+      return fail(MRBO_ERR_ARG, "gp_optimize_multi: bounds [%g, %g] of hyperparameter %d", lower[t], upper[t], t);
+    mp.lo[t] = lower[t];
+    mp.hi[t] = upper[t];
+  }
+  mp.iterations = o ? o->iterations : 0;
+  mp.m = o ? o->history : 0;
+  mp.g_tol = o ? o->g_tol : 0.0;
+  mp.c1 = o ? o->c1 : 0.0;
+  if (mp.iterations < 0) return fail(MRBO_ERR_ARG, "gp_optimize_multi: iterations=%d", mp.iterations);
+  if (mp.m < 0 || mp.m > MLE_HIST_MAX)
+    return fail(MRBO_ERR_ARG, "gp_optimize_multi: history=%d outside 1..%d", mp.m, MLE_HIST_MAX);
+  if (!(mp.g_tol >= 0.0) || !std::isfinite(mp.g_tol) || !(mp.c1 >= 0.0) || !std::isfinite(mp.c1))
+    return fail(MRBO_ERR_ARG, "gp_optimize_multi: g_tol=%g c1=%g", mp.g_tol, mp.c1);
+  if (flags & ~(uint32_t)MRBO_FLAG_HOST_POINTERS)
+    return fail(MRBO_ERR_ARG, "gp_optimize_multi: flags: only MRBO_FLAG_HOST_POINTERS");
+  if (mp.iterations == 0) mp.iterations = 30;
+  if (mp.m == 0) mp.m = 10;
+  if (mp.g_tol == 0.0) mp.g_tol = 1e-8;
+  if (mp.c1 == 0.0) mp.c1 = 1e-4;
+  mp.S = ns;
+  mp.nt = nt;
+
+  hipStream_t st = (hipStream_t)stream;
+  const bool host = flags & MRBO_FLAG_HOST_POINTERS;
+  const int d = s->d, N = s->N;
+  const size_t S = (size_t)ns, NT = (size_t)nt * S, P = MLE_STEPS, M = (size_t)mp.m;
+  // the starts of a host call travel with the data sets
+  GpFitStaged f(host ? NT : 0, (size_t)d * N * S + (size_t)N * S + S);
+  // the minimiser's device block: doubles [trial | ll | ∇ll | s | y | α], then ints [status | ring | check];
+  // a host call's outputs [theta | nll | grad | iters] in a block of their own, one copy back
+  const size_t n_dbl = NT * P + P * S + NT * P + 2 * NT * M + M * S, n_int = P * S + 3 * S + MLE_NCHK;
+  const size_t out_bytes = sizeof(double) * (2 * NT + S) + sizeof(int32_t) * S;
+  double* dw = (double*)f.sg.slot(sizeof(double) * n_dbl + sizeof(int32_t) * n_int);
+  char* dout = host ? (char*)f.sg.slot(out_bytes) : nullptr;
+  if (!dw || (host && !dout)) return fail(MRBO_ERR_NOMEM, "gp_optimize_multi: device buffers");
+  Pinned pin_out(host ? out_bytes : 0), pin_chk(sizeof(int32_t) * MLE_NCHK);
+  if ((host && !pin_out.p) || !pin_chk.p) return fail(MRBO_ERR_NOMEM, "pinned staging");
+  struct EventGuard {
+    CheckEvents c;
+    ~EventGuard() { c.give(); }
+  } evs;
+  evs.c.take();
+  if (!evs.c.ok) return fail(MRBO_ERR_HIP, "gp_optimize_multi: hipEventCreate");
+  mp.trial = dw;
+  double* dll_ = mp.trial + NT * P;
+  double* dgll = dll_ + P * S;
+  mp.hs = dgll + NT * P;
+  mp.hy = mp.hs + NT * M;
+  mp.al = mp.hy + NT * M;
+  int* dst = (int*)(mp.al + M * S);
+  mp.ring = dst + P * S;
+  mp.check = mp.ring + 3 * S;
+  mp.ll = dll_;
+  mp.gll = dgll;
+  mp.status = dst;
+  mp.x = host ? (double*)dout : theta;
+  mp.f = host ? mp.x + NT : nll;
+  mp.g = host ? mp.f + S : grad;
+  mp.it = host ? (int*)(mp.g + NT) : (int*)iters;
+  f.q.ll = dll_;
+  f.q.grad = dgll;
+  f.q.status = dst;
+  // from the staging copy on every return path synchronises the stream first
+  if (const int rc = gp_fit_stage(s, ns, nt, theta0, P * S, st, f)) return rc;
+  mp.theta0 = host ? f.q.thetas : theta0;
+  int32_t* const hchk = (int32_t*)pin_chk.p;
+  auto bail = [&](const char* what, hipError_t e) {   // the launches queued may still use every buffer
+    if (hipStreamSynchronize(st) != hipSuccess) {
+      f.sg.abandon();
+      f.pin_in.abandon();
+      pin_out.abandon();
+      pin_chk.abandon();
+      evs.c.ok = false;
+    }
+    return fail(MRBO_ERR_HIP, "gp_optimize_multi: %s: %s", what, hipGetErrorString(e));
+  };
+  launch_mle_init(st, mp);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return bail("init launch", e);
+  // Round j = 1 evaluates the clipped starts (grid (1, S)), every later round one line search per
+  // problem (grid (12, S)); the step kernel after it accepts, updates and proposes.  The rounds
+  // follow each other on the stream; behind them the host reads round j's count of running
+  // problems LAG rounds later.  Once it is 0 every problem is frozen, so the rounds already
+  // queued change no output.  The budget ends the loop after iterations + 1 rounds at the latest:
+  // the step kernel of that round stops whatever still runs.
+  constexpr int LAG = 2;
+  const int max_rounds = mp.iterations + 1;
+  int j = 0, stopped_at = 0;
+  auto read_check = [&](int r) -> hipError_t {   // round r ≥ 1 (its slot not yet reused)
+    const int k = (r - 1) % MLE_NCHK;
+    const hipError_t e = hipEventSynchronize(evs.c.ev[k]);
+    if (e == hipSuccess && hchk[k] == 0 && !stopped_at) stopped_at = r;
+    return e;
+  };
+  while (j < max_rounds && !stopped_at) {
+    ++j;
+    const int k = (j - 1) % MLE_NCHK;
+    f.q.thetas = j == 1 ? mp.x : mp.trial;
+    hipError_t e = gp_fit_launch(j == 1 ? 1 : (int)P, ns, st, f.q);
+    if (e != hipSuccess) return bail("fit launch", e);
+    launch_mle_step(j == 1, k, st, mp);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hchk + k, mp.check + k, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(evs.c.ev[k], st);
+    if (e == hipSuccess && j > LAG) e = read_check(j - LAG);
+    if (e != hipSuccess) return bail("step", e);
+  }
+  for (int r = std::max(1, j - LAG + 1); r <= j; ++r)   // the checks still in flight
+    if (const hipError_t e = read_check(r); e != hipSuccess) return bail("hipEventSynchronize", e);
+  if (host)
+    if (const hipError_t e = hipMemcpyAsync(pin_out.p, dout, out_bytes, hipMemcpyDeviceToHost, st); e != hipSuccess)
+      return bail("copy back", e);
+  if (const hipError_t e = hipStreamSynchronize(st); e != hipSuccess) {
+    f.sg.abandon();
+    f.pin_in.abandon();
+    pin_out.abandon();
+    pin_chk.abandon();
+    evs.c.ok = false;
+    return fail(MRBO_ERR_HIP, "gp_optimize_multi: hipStreamSynchronize: %s", hipGetErrorString(e));
+  }
+  if (host) {
+    const double* h = (const double*)pin_out.p;
+    std::memcpy(theta, h, sizeof(double) * NT);
+    std::memcpy(nll, h + NT, sizeof(double) * S);
+    std::memcpy(grad, h + NT + S, sizeof(double) * NT);
+    std::memcpy(iters, h + 2 * NT + S, sizeof(int32_t) * S);
+  }
+  result[0] = j;                             // rounds launched
+  result[1] = stopped_at ? stopped_at : j;   // the round after which no problem ran
+  return MRBO_OK;
+}
 
 int mrbo_plan_set_order(mrbo_plan_t* P, const int32_t* order, int64_t n) {
   if (!P) return fail(MRBO_ERR_ARG, "null plan");

@@ -12,7 +12,8 @@ Compute runs in libmrbo.so (hand-written HIP for gfx950); see include/mrbo.h.
 """
 from .decision_rules import EI, LCB, POI, DecisionRule, RandomAcquisition, get_name
 from .kernels import Matern12, Matern32, Matern52, Periodic, SquaredExponential, eval_KxX, eval_KXX
-from .mle import grad_log_likelihood, gp_fit_batch, log_likelihood, optimize
+from .mle import (gp_fit_batch, gp_optimize_multi, grad_log_likelihood, lbfgs_scalar, log_likelihood, optimize,
+                  optimize_multi)
 from .optimizers import Adam, StandardSGA, update
 from .rollout import (simulate_trajectory_ghq, simulate_trajectory_ghq_batch, simulate_trajectory_mc,
                       simulate_trajectory_mc_batch)

@@ -36,7 +36,7 @@ EXPORTS = [
     "mrbo_initial_guesses", "mrbo_dual_uniform", "mrbo_last_kernel_ms", "mrbo_gp_fit", "mrbo_gp_fit_theta",
     "mrbo_plan_info", "mrbo_last_gp_fit_ms", "mrbo_plan_set_order", "mrbo_base_solve", "mrbo_sga_step",
     "mrbo_kernel_times", "mrbo_merge_moments", "mrbo_adam_step", "mrbo_stochastic_solve",
-    "mrbo_plan_order_longest_first", "mrbo_plan_create_batch", "mrbo_gp_fit_multi",
+    "mrbo_plan_order_longest_first", "mrbo_plan_create_batch", "mrbo_gp_fit_multi", "mrbo_gp_optimize_multi",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM = 0, 1
@@ -63,6 +63,12 @@ class SolveOpts(ctypes.Structure):
     _fields_ = [("optimizer", ctypes.c_int32), ("iterations", ctypes.c_int32), ("eta", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("sample_size", ctypes.c_double)]
+
+
+class MleOpts(ctypes.Structure):
+    """mrbo_mle_opts_t (include/mrbo.h); a zero field takes its default."""
+    _fields_ = [("iterations", ctypes.c_int32), ("history", ctypes.c_int32), ("g_tol", ctypes.c_double),
+                ("c1", ctypes.c_double)]
 
 
 _lib = None
@@ -116,6 +122,9 @@ def load():
                                     _vp, _vp, _vp, ctypes.c_uint32, _vp]
     L.mrbo_gp_fit_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
                                     _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
+    L.mrbo_gp_optimize_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                         ctypes.POINTER(MleOpts), _vp, _vp, _vp, _vp,
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
     L.mrbo_last_kernel_ms.argtypes = [_vp]
     L.mrbo_last_kernel_ms.restype = ctypes.c_double
     L.mrbo_plan_info.argtypes = [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]

@@ -206,7 +206,7 @@ def _check_parallel_trials(parallel_trials, reuse_surrogate):
 def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, mc_samples=200, batch_size=8,
         sgd_iterations=50, optimize=False, seed=1906, device=0, log=print, rules=("ei", "poi", "lcb"), eta=0.01,
         initial_observations=INITIAL_OBSERVATIONS, solver="sga", fmini_over_capacity=True, incumbent=True,
-        reuse_surrogate=True, parallel_trials=1):
+        reuse_surrogate=True, parallel_trials=1, device_mle=False):
     """The experiment loop; `rules` selects a subset of the reference's three acquisitions (all by
     default, as nonmyopic_bayesopt.jl), `eta` the StandardSGA step of the build-defined solver
     (default 0.01, StandardSGA's own default, optimizers.jl:9),
@@ -222,7 +222,9 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     lockstep -- every budget step is ONE batched acquisition solve for their k surrogates (a
     surrogate batch, rollout_solve_multi), then each trial conditions (and optionally runs MLE) on
     its own surrogate.  The trials observe exactly what they observe one after another; `times`
-    records the batched solve's wall time for each of its trials."""
+    records the batched solve's wall time for each of its trials.
+    device_mle=True (with optimize): the MLE refit's minimisation runs as one device-resident call
+    (mle.optimize(..., device=True)); the default keeps the host-driven loop."""
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
@@ -274,7 +276,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 if optimize:   # every trial has conditioned: one batched refit for the chunk
                     from .mle import optimize_multi
                     t0 = time.perf_counter()
-                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS)
+                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                     mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start in zip(chunk, surs, rec, ell_starts):
                 log(f"{acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, {r['times'].sum():.2f} s of solves")
@@ -309,7 +311,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 sur.condition(xnext, float(testfn.f(xnext)))
                 if optimize:
                     from .mle import optimize as mle_optimize
-                    mle_optimize(sur, KERNEL_LBS, KERNEL_UBS)
+                    mle_optimize(sur, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                 minobs[b] = float(np.min(sur.get_active_observations()))
             log(f"{acq} trial {trial + 1}/{trials}: gap {gaps[-1]:.4f}, {times.sum():.2f} s of solves")
             for metric, data in zip(METRICS, (times, gaps, allocs, regrets, minobs)):
@@ -326,7 +328,8 @@ MYOPIC_RULES = {"ei": (EI, 0.0), "poi": (POI, 0.0), "lcb": (LCB, 2.0)}   # :151-
 
 def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed=1906, device=0, log=print,
                rules=("ei", "poi", "lcb"), optimize=True, initial_observations=INITIAL_OBSERVATIONS,
-               reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False, parallel_trials=1):
+               reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False, parallel_trials=1,
+               device_mle=False):
     """myopic_bayesopt.jl's loop: per budget step xnext = multistart_base_solve!(sur, …; guesses =
     generate_initial_guesses(starts, lbs, ubs), θfixed) -- the deterministic multistart local solve of
     the analytic acquisition on the base surrogate (:224-233), here mrbo_base_solve on the device --
@@ -348,7 +351,9 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     minimiser is not an observed point (within 1e-6 of a box width) is taken, to test whether
     re-observing a point explains a difference; every trial records its repeated observations.
     parallel_trials=k > 1 (needs reuse_surrogate=False, else ValueError): up to k trials advance in
-    lockstep, every budget step one mrbo_base_solve launch on their k surrogates (base_solve_multi)."""
+    lockstep, every budget step one mrbo_base_solve launch on their k surrogates (base_solve_multi).
+    device_mle=True: optimize!'s minimisation runs as one device-resident call
+    (mle.optimize(..., device=True)); the default keeps the host-driven loop."""
     from .rbf_optim import base_solve_batch, base_solve_multi, findmin_candidates, multistart_base_solve
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     from .utils import generate_initial_guesses
@@ -410,7 +415,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                 if optimize:   # every trial has conditioned: one batched refit for the chunk
                     from .mle import optimize_multi
                     t0 = time.perf_counter()
-                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS)
+                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                     mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start, rp in zip(chunk, surs, rec, ell_starts, reps):
                 log(f"myopic {acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, "
@@ -458,7 +463,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                 sur.condition(xnext, float(testfn.f(xnext)))
                 if optimize:
                     from .mle import optimize as mle_optimize
-                    mle_optimize(sur, KERNEL_LBS, KERNEL_UBS)
+                    mle_optimize(sur, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                 minobs[b] = float(np.min(sur.get_active_observations()))
             log(f"myopic {acq} trial {trial + 1}/{trials}: gap {gaps[-1]:.4f}, {times.sum():.2f} s of solves")
             for metric, data in zip(METRICS, (times, gaps, allocs, regrets, minobs)):
@@ -486,6 +491,8 @@ def parse(argv=None):
     ap.add_argument("--parallel-trials", type=int, default=1,
                     help="trials advanced in lockstep, one batched acquisition solve per budget step "
                          "(> 1 runs a fresh surrogate per trial)")
+    ap.add_argument("--device-mle", action="store_true",
+                    help="with --optimize: run the MLE refit's minimisation as one device-resident call")
     return ap.parse_args(argv)
 
 
@@ -493,7 +500,8 @@ def main(argv=None):
     a = parse(argv)
     run(a.function_name, a.output_dir, budget=a.budget, trials=a.trials, starts=a.starts, horizon=a.horizon,
         mc_samples=a.mc_samples, batch_size=a.batch_size, sgd_iterations=a.sgd_iterations, optimize=a.optimize,
-        seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1)
+        seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1,
+        device_mle=a.device_mle)
 
 
 if __name__ == "__main__":

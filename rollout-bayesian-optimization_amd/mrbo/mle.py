@@ -13,8 +13,11 @@ box-constrained stationary point of the same objective from the same start.
 The refits of k lockstep BO trials run together (no reference counterpart): gp_fit_multi is one
 launch for S surrogates × P candidates (mrbo_gp_fit_multi), projected_lbfgs_multi advances the S
 minimisations in lockstep through the same per-problem code, optimize_multi is optimize for a list.
+gp_optimize_multi runs those S minimisations as one device-resident call (mrbo_gp_optimize_multi:
+no host round trip per line search); lbfgs_scalar is the specification its step kernel is held to.
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -220,10 +223,158 @@ def projected_lbfgs_multi(fg_multi, x0s, lower, upper, iterations=30, g_tol=1e-8
     return out
 
 
-def optimize(s, lowerbounds, upperbounds, iterations=30):
+def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1=1e-4):
+    """projected_lbfgs restated on Python floats: every operation of _lbfgs_problem written out
+    one rounding at a time -- a dot product is a0*b0 + a1*b1 + ... left to right, a norm the square
+    root of that, nothing fused.  This is the specification of the device minimiser
+    (mrbo_gp_optimize_multi's step kernel, csrc/mrbo_mle.hip, performs these operations in this
+    order in fp64), so the two agree bit for bit on the same evaluations.  For one variable it
+    equals projected_lbfgs exactly (a dot product is one multiplication); for more, numpy's `@` may
+    fuse its multiply-adds and the two can differ in the last bits.  Returns (x, f, g, iterations)
+    with x and g as arrays."""
+    lo = [float(v) for v in np.asarray(lower, float).ravel()]
+    hi = [float(v) for v in np.asarray(upper, float).ravel()]
+    n = len(lo)
+    R = range(n)
+
+    def clip(v, i):
+        if v < lo[i]:
+            v = lo[i]
+        if v > hi[i]:
+            v = hi[i]
+        return v
+
+    def dot(a, b):
+        r = a[0] * b[0]
+        for i in range(1, n):
+            r = r + a[i] * b[i]
+        return r
+
+    def absmax(a):          # np.max(np.abs(a)): a NaN stays
+        r = abs(a[0])
+        for i in range(1, n):
+            v = abs(a[i])
+            if v > r or v != v:
+                r = v
+        return r
+
+    def evaluate(points):
+        f, g = fg_batch(np.array(points, dtype=np.float64).reshape(len(points), n))
+        return [float(v) for v in f], [[float(v) for v in row] for row in np.asarray(g).reshape(len(points), n)]
+
+    x = [clip(float(v), i) for i, v in enumerate(np.asarray(x0, float).ravel())]
+    ft, gt = evaluate([x])
+    f, g = ft[0], gt[0]
+    S, Y = [], []
+    it = 0
+    while it < iterations:
+        it += 1
+        free = [not ((x[i] <= lo[i] and g[i] > 0) or (x[i] >= hi[i] and g[i] < 0)) for i in R]
+        if not any(free) or all(abs(g[i]) <= g_tol for i in R if free[i]):
+            it -= 1
+            break
+        # two-loop recursion on the free variables
+        q = [g[i] if free[i] else 0.0 for i in R]
+        al = [0.0] * len(S)
+        for j in reversed(range(len(S))):
+            a = dot(S[j], q) / dot(Y[j], S[j])
+            al[j] = a
+            q = [q[i] - a * Y[j][i] for i in R]
+        if S:
+            sc = dot(S[-1], Y[-1]) / dot(Y[-1], Y[-1])
+            q = [q[i] * sc for i in R]
+        else:
+            mx = absmax(q)                        # first step: at most unit length
+            if 1.0 > mx:
+                mx = 1.0
+            q = [q[i] / mx for i in R]
+        for j in range(len(S)):
+            b = dot(Y[j], q) / dot(Y[j], S[j])
+            q = [q[i] + (al[j] - b) * S[j][i] for i in R]
+        p = [-(q[i] if free[i] else 0.0) for i in R]
+        if dot(g, p) >= 0:                        # not a descent direction: steepest descent
+            p = [-(g[i] if free[i] else 0.0) for i in R]
+        trial = [[clip(x[i] + float(st) * p[i], i) for i in R] for st in _STEPS]
+        ft, gt = evaluate(trial)
+        k = -1
+        for kk in range(len(trial)):
+            d = [trial[kk][i] - x[i] for i in R]
+            if math.isfinite(ft[kk]) and ft[kk] <= f + c1 * dot(d, g):
+                k = kk
+                break
+        if k < 0:
+            break
+        xn, fn, gn = trial[k], ft[k], gt[k]
+        sk = [xn[i] - x[i] for i in R]
+        yk = [gn[i] - g[i] for i in R]
+        thr = math.sqrt(dot(sk, sk)) * math.sqrt(dot(yk, yk))
+        if 1e-300 > thr:
+            thr = 1e-300
+        if dot(sk, yk) > 1e-12 * thr:
+            S.append(sk)
+            Y.append(yk)
+            if len(S) > m:
+                S.pop(0)
+                Y.pop(0)
+        moved = absmax(sk)
+        x, f, g = xn, fn, gn
+        if moved == 0.0:
+            break
+    return np.array(x), f, np.array(g), it
+
+
+def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, iterations=30, history=10):
+    """The S minimisations of optimize_multi as ONE device-resident call (mrbo_gp_optimize_multi):
+    the data sets are staged once, and every line-search round -- one fit launch of grid (12, S) and
+    one step kernel -- follows the last on the stream without a host round trip.  Problem q starts
+    at theta0[q] (default: the surrogates' current θ) and ends, bit for bit, where lbfgs_scalar
+    driven by gp_fit_batch(surs[q], ·) ends.  The surrogates are left untouched.  A Periodic
+    kernel with theta0 of shape (S, 1) is minimised over ℓ alone, every data set at its own period.
+
+    Returns dict(theta (S, nt), neg_log_likelihood (S,), gradient (S, nt), iterations (S,), rounds
+    -- fit launches made, the start's included --, stopped_at -- the round after which no problem
+    ran, 1 + max(iterations))."""
+    surs = list(surs)
+    d, n, nt = check_fit_batch(surs)
+    if lowerbounds is None or upperbounds is None:
+        raise ValueError("gp_optimize_multi needs lowerbounds and upperbounds")
+    if int(iterations) < 1 or not 1 <= int(history) <= 16:
+        raise ValueError(f"iterations = {iterations}, history = {history}: at least 1, and 1..16")
+    S = len(surs)
+    th0 = np.stack([s.ψ.θ for s in surs]) if theta0 is None else np.asarray(theta0, dtype=np.float64)
+    if th0.shape[:1] == (S,) and th0.ndim <= 2 and th0.size == S and nt == 2:
+        nt = 1          # Periodic over ℓ alone: every data set keeps its own period
+    if th0.shape not in ((S, nt), (S,) if nt == 1 else None):
+        raise ValueError(f"theta0 has shape {th0.shape}: (S, nt) = ({S}, {nt})")
+    th0 = np.ascontiguousarray(th0.reshape(S, nt), dtype=np.float64)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lowerbounds, dtype=np.float64).ravel(), (nt,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upperbounds, dtype=np.float64).ravel(), (nt,)))
+    L = _lib.load()
+    dp = ctypes.POINTER(ctypes.c_double)
+    keep = [(np.asfortranarray(s.X[:, :n]), np.ascontiguousarray(s.y[:n])) for s in surs]
+    sds = (_lib.SurrogateDesc * S)(*[
+        _lib.SurrogateDesc(d, n, int(s.ψ.kind), float(s.ψ.lengthscale), float(s.σn2), float(s.fmini()),
+                           X.ctypes.data_as(dp), None, n, None, y.ctypes.data_as(dp), float(s.ψ.period))
+        for s, (X, y) in zip(surs, keep)])
+    opts = _lib.MleOpts(int(iterations), int(history), 0.0, 0.0)
+    th, f, g = np.zeros((S, nt)), np.zeros(S), np.zeros((S, nt))
+    its = np.zeros(S, dtype=np.int32)
+    res = (ctypes.c_int32 * 2)()
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+    _lib.check(L.mrbo_gp_optimize_multi(sds, S, nt, vp(th0), vp(lo), vp(hi), ctypes.byref(opts), vp(th), vp(f), vp(g),
+                                        vp(its), res, _lib.MRBO_FLAG_HOST_POINTERS, None))
+    return dict(theta=th, neg_log_likelihood=f, gradient=g, iterations=its, rounds=int(res[0]),
+                stopped_at=int(res[1]))
+
+
+def optimize(s, lowerbounds, upperbounds, iterations=30, device=False):
     """optimize!(s; lowerbounds, upperbounds) (radial_basis_surrogates.jl:805-829): maximise the
     log likelihood over the kernel hyperparameters (ℓ; Periodic ℓ and p) within the box, then
-    set_kernel! at the optimum."""
+    set_kernel! at the optimum.  device=True runs the minimisation as one device-resident call
+    (gp_optimize_multi with S = 1)."""
+    if device:
+        return optimize_multi([s], lowerbounds, upperbounds, iterations, device=True)[0]
+
     def fg(T):
         r = gp_fit_batch(s, T)
         f = np.where(r["status"] == 0, -r["ll"], np.nan)
@@ -235,14 +386,25 @@ def optimize(s, lowerbounds, upperbounds, iterations=30):
     return dict(theta=θ, neg_log_likelihood=f, gradient=g, iterations=it)
 
 
-def optimize_multi(surs, lowerbounds, upperbounds, iterations=30):
+def optimize_multi(surs, lowerbounds, upperbounds, iterations=30, device=False):
     """optimize for the surrogates of k lockstep trials: the minimisations advance together, and
     each round's evaluations -- one line search per surrogate still running -- are ONE
     gp_fit_multi launch instead of one launch per surrogate.  Every surrogate ends with the θ,
     objective, gradient and iteration count optimize alone gives it.  Returns optimize's dict per
-    surrogate."""
+    surrogate.  device=True runs the whole minimisation in one device-resident call
+    (gp_optimize_multi: no host round trip per round) and then set_kernel on the host as before."""
     surs = list(surs)
     check_fit_batch(surs)
+    from .kernels import set_hyperparameters
+    if device:
+        r = gp_optimize_multi(surs, None, lowerbounds, upperbounds, iterations)
+        out = []
+        for q, s in enumerate(surs):
+            θ = r["theta"][q].copy()
+            s.set_kernel(set_hyperparameters(s.ψ, θ))
+            out.append(dict(theta=θ, neg_log_likelihood=float(r["neg_log_likelihood"][q]),
+                            gradient=r["gradient"][q].copy(), iterations=int(r["iterations"][q])))
+        return out
 
     def fg_multi(idx, T):
         r = gp_fit_multi([surs[i] for i in idx], T)
@@ -250,7 +412,6 @@ def optimize_multi(surs, lowerbounds, upperbounds, iterations=30):
         return f, -r["grad"]
 
     res = projected_lbfgs_multi(fg_multi, [s.ψ.θ.copy() for s in surs], lowerbounds, upperbounds, iterations)
-    from .kernels import set_hyperparameters
     out = []
     for s, (θ, f, g, it) in zip(surs, res):
         s.set_kernel(set_hyperparameters(s.ψ, θ))
