@@ -333,7 +333,11 @@ __device__ __forceinline__ double fold_all(double v) {
 // Transpose-reduce K per-lane values across the 64 lanes: log2(K) transpose steps (pairs
 // across lane bits 5, 4, …) leave one partial per lane, then plain all-reduce steps finish;
 // one lane per group writes red[idx].  Cost ≈ K + log2(64/K) exchanges instead of 6K.
-// The pairing and summation order are fixed: the result is deterministic.
+// The pairing and summation order are fixed: the result is deterministic.  Lane l adds the value of
+// lane l^32, then l^16 (permlane swaps), then l^15, l^7 (DPP row_mirror, row_half_mirror: the mirror
+// image within the row of 16 resp. 8 lanes, not l^8 and l^4), then l^2 and l^1 (quad_perm); the
+// transpose steps of K > 1 come first and use the same partners.  tests/test_gpu_primitives.py
+// holds the bits of every K to a NumPy emulation of this butterfly.
 template <int K>
 __device__ __forceinline__ void wave_reduce(double (&v)[K], double* red, int lane) {
   constexpr int S = (K == 1) ? 0 : (K == 2) ? 1 : (K == 4) ? 2 : (K == 8) ? 3 : (K == 16) ? 4 : 5;
@@ -441,7 +445,10 @@ __device__ __forceinline__ double fma_sc(double a, double b) {
 // exp(x), inlined: the device library's algorithm and coefficients in the same operation order
 // (Cody–Waite reduction by ln2, degree-11 polynomial, 2^k by v_ldexp_f64, overflow / underflow
 // selects), so results are bit-identical to exp() -- without a call's prologue (scratch save of
-// a VGPR and a full s_waitcnt on entry) or VALU moves for the coefficients.
+// a VGPR and a full s_waitcnt on entry) or VALU moves for the coefficients.  Checked on the device
+// (tests/test_gpu_primitives.py): the same bits as exp() over [−750, 710], at ±0, subnormals, both
+// range ends, ±1024, ±1075, ±inf and NaN; within 1 ulp of the exact value wherever that is normal
+// (measured maximum 0.78 ulp).
 __device__ __forceinline__ double fexp(double x) {
   const double k = __builtin_rint(x * sconst<0x652b82feu, 0x3ff71547u>());            // x·log2(e)
   double r = fma(sconst<0xfefa39efu, 0xbfe62e42u>(), k, x);                          // − k·ln2_hi
@@ -472,8 +479,9 @@ __device__ __forceinline__ double fexp(double x) {
 __device__ __forceinline__ double xexp(double x) { return fexp(x); }
 
 // √s and 1/√s (s > 0) from one hardware reciprocal square root and two Newton–Raphson steps
-// y ← y(1.5 − ½s·y²): ~1 ulp, and a much shorter dependent chain than a correctly rounded
-// sqrt followed by an IEEE division (Cholesky pivots of the Newton step and of gp_draw).
+// y ← y(1.5 − ½s·y²): within 2 ulp for s in [1e-290, 1e290] (measured maxima: √s 1.39 ulp, 1/√s
+// 0.94 ulp), and a much shorter dependent chain than a correctly rounded sqrt followed by an IEEE
+// division (Cholesky pivots of the Newton step and of gp_draw).
 __device__ __forceinline__ void sqrt_rsqrt(double s, double& r, double& ir) {
   const double h = 0.5 * s;
   double y = __builtin_amdgcn_rsq(s);
@@ -484,8 +492,9 @@ __device__ __forceinline__ void sqrt_rsqrt(double s, double& r, double& ir) {
 }
 
 // √s for s ≥ 0 (sums of squares) from sqrt_rsqrt: ~8 dependent operations instead of the IEEE
-// expansion's ~14, within 2 ulp.  s ≤ 1e-290 (zero, subnormal) gives 0 and NaN stays NaN; the
-// Matérn-5/2 forms and the certificates absorb a subnormal's root exactly (1 + 1e-145 = 1).
+// expansion's ~14, within 2 ulp (measured maximum 1.39 ulp).  s ≤ 1e-290 (zero, subnormal, negative)
+// gives ±0 and NaN stays NaN; the Matérn-5/2 forms and the certificates absorb a subnormal's root
+// exactly (1 + 1e-145 = 1).
 __device__ __forceinline__ double fast_sqrt0(double s) {
   double r, ir;
   sqrt_rsqrt(s, r, ir);
@@ -516,13 +525,17 @@ struct Radial {
 //   k(r) = ψ,   ∇k(r) = g1·r,   ∇²k(r) = g2·r rᵀ + g1·I.
 // The closed forms cancel the 1/ρ factors for Matérn-5/2 and SE (no division, no ρ = 0
 // branch); Matérn-3/2 and -1/2 keep one reciprocal.  At ρ = 0, g1 = ψ''(0) and g2 = 0 — the
-// reference's ρ = 0 branches (∇k = 0, ∇²k = ψ''(0)·I).
+// reference's ρ = 0 branches (∇k = 0, ∇²k = ψ''(0)·I).  g2 = 0 there holds for the kinds that branch
+// on ρ > 0 (Matérn-3/2, -1/2); the branch-free forms (Matérn-5/2, SE, Periodic) return the finite
+// limit of g2, which multiplies r rᵀ = 0.  Matérn-1/2 g2 ≈ c/ρ³ is +inf for 0 < ρ below ≈ 1e-103.
 __device__ __forceinline__ void rad_eval(const Radial& k, double rho2, double& psi, double& g1, double& g2) {
   const double c = k.cK;
   if (k.kind == 4) {
     // Periodic (:98-103) ψ = exp(−2 sin²(πρ/p)/ℓ²).  With B = 2π/p, A = B/ℓ², t = Bρ:
     //   g1 = ψ'/ρ = −ψ A B sinc t,   g2 = ψ B² (A² sinc²t + A B (sinc t − cos t)/t²)
-    // (sinc t − cos t)/t² = (sin t − t cos t)/t³ by its series below t = 0.1 (cancellation)
+    // (sinc t − cos t)/t² = (sin t − t cos t)/t³ by its series below t = 0.1 (cancellation).
+    // sinc t itself is the quotient for every t > 0 (a quotient does not cancel): its three-term
+    // series below t = 0.1 was off by t⁶/5040, 2e-10 at the switch, in g1 and in the A² term of g2
     const double B = k.cP, A = B * c;
     const double rho = sqrt(rho2), t = B * rho;
     double su, cu;
@@ -531,7 +544,7 @@ __device__ __forceinline__ void rad_eval(const Radial& k, double rho2, double& p
     const double st = 2.0 * su * cu, ct = fma(-2.0 * su, su, 1.0);
     const double t2 = t * t;
     const bool small = t < 0.1;
-    const double sinc = small ? fma(t2, fma(t2, 1.0 / 120.0, -1.0 / 6.0), 1.0) : st / t;
+    const double sinc = (t > 0.0) ? st / t : 1.0;
     const double f = small ? fma(t2, fma(t2, fma(t2, -1.0 / 45360.0, 1.0 / 840.0), -1.0 / 30.0), 1.0 / 3.0)
                            : (st - t * ct) / (t2 * t);
     g1 = -psi * A * B * sinc;
@@ -572,6 +585,12 @@ __device__ __forceinline__ void rad_eval(const Radial& k, double rho2, double& p
 // Two radial evaluations at once (a base row and a fantasy row of the same lane): for Matérn-5/2
 // both exponentials come from one leaf call whose two inlined fexp chains interleave, instead of
 // two calls in sequence.  Same closed forms as rad_eval; other kernels take two rad_eval calls.
+// ψ and g2 have the bits of rad_eval.  g1 need not: the compiler may fuse 1.0 + s with s = c·ρ into
+// one FMA here, where the product stands in the same block, and not in rad_eval, whose product
+// precedes the branch on the kind (compiled standalone with a run-time kind: 3 % of the points
+// differ, by at most 3 ulp).  Both roundings are within the (1 + s)-ulp bound of the tests; the
+// source is left as it is, because the Newton iteration counts of the long C4 solves are held to
+// the oracle's within a few steps and move with a last-bit change of g1.
 struct Exp2 {
   double a, b;
 };
@@ -603,10 +622,17 @@ __device__ __forceinline__ void rad_eval2(const Radial& k, double rho2a, double 
 // E = exp(−z²/2) = exp(−u²):  φ = E/√(2π),  the tail Q = P(Z > |z|) = ½·E·erfcx(u), and
 // Φ = Q (z ≤ 0) or 1 − Q (z > 0).  erfcx(u) = P(t)/(1 + 2u) with t = (u − K)/(u + K), K = 3.5,
 // P a degree-23 polynomial from the Chebyshev series of (1 + 2u)·erfcx(u) on u ∈ [0, ∞)
-// (tools/fit_erfcx.py, mpmath at 60 digits): max relative error 4.2e-16 over [0, 27] in fp64.
+// (tools/fit_erfcx.py, mpmath at 60 digits).  The fit script's own figure, 4.2e-16 over [0, 27], is
+// that of a power-basis Horner evaluation in Python with K = 4, not of this scheme (K = 3.5, Estrin
+// halves, v_rcp_f64 + two Newton steps, FMAs).  Measured on the device against mpmath
+// (tests/test_gpu_primitives.py, z ∈ [−36, 36]; an ulp is that of the exact value): the ratio Φ/φ =
+// √(π/2)·erfcx(u), in which E drops out, within 4.8 ulp for z ≤ 0; φ within 1.4 + z²/2 ulp and Φ
+// (z ≤ 0) within 3.3 + z²/2 ulp, z²/2 being the rounding of z² in E's exponent; |Φ − exact| ≤ 2e-16
+// for z > 0; φ + zΦ within 4.8·(1 + z²) ulp on [−36, 0], where the two terms cancel to 1/z² of either.
 // Replaces two leaf calls (exp, erfc -- the latter with exponentials of its own) evaluated in
 // sequence by two independent inline chains (the exponential and the polynomial).  Sharing E
-// also makes φ + zΦ (the EI tail, where both nearly cancel) carry E's rounding as one factor.
+// also makes φ + zΦ (the EI tail, where both nearly cancel) carry E's rounding as one factor: the
+// same sum from libm's exp and erfc in fp64 is off by up to 1.8e3·(1 + z²) ulp on that range.
 // Not bit-identical to libm erfc; GPU-vs-oracle parity is a tolerance.
 struct PhiPair {
   double phi, Phi;
