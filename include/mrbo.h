@@ -12,6 +12,8 @@
  *   mrbo_eto_reduce        the mean / std(n-1) tail of simulate_trajectory_mc, rollout.jl:328-339
  *   mrbo_stochastic_solve  stochastic_solve utils.jl:235-265 (eswavs + StandardSGA / Adam update!)
  *                          over a restart batch, the whole ascent in one call
+ *   mrbo_rollout_solve     the build's acquisition solve of a BO step (the reference's rollout solver
+ *                          is undefined): the ascent, the final evaluation and the pick in one call
  *   mrbo_eval_base         eval(s::Surrogate, x, θ) radial_basis_surrogates.jl:224-310 (μ, σ, ∇, Hα)
  *   mrbo_rnstream          gen_low_discrepancy_sequence utils.jl:65-74 (Sobol→Box–Muller(log10))
  *   mrbo_initial_guesses   generate_initial_guesses utils.jl:145-153
@@ -254,7 +256,11 @@ int mrbo_adam_step(mrbo_plan_t* plan, const double* eto, double* x0s, int32_t* a
  *            the reference would have thrown -- the Julia method throws)
  * Arrays are device pointers unless MRBO_FLAG_HOST_POINTERS (then staged once for the whole
  * ascent); synchronises `stream` before returning.                                            */
-typedef enum { MRBO_OPT_SGA = 0, MRBO_OPT_ADAM = 1 } mrbo_optimizer_t;
+typedef enum {
+  MRBO_OPT_SGA = 0,
+  MRBO_OPT_ADAM = 1,
+  MRBO_OPT_BOX_ADAM = 2   /* mrbo_rollout_solve only; mrbo_stochastic_solve refuses it */
+} mrbo_optimizer_t;
 typedef struct {
   int32_t optimizer;    /* mrbo_optimizer_t                                                  */
   int32_t iterations;   /* ≥ 1; the reference's loop: 50                                      */
@@ -267,6 +273,73 @@ typedef struct {
 int mrbo_stochastic_solve(mrbo_plan_t* plan, double* x0s, const double* rnstream, const double* xstarts,
                           const double* dual_y_dx, const mrbo_solve_opts_t* opts, double* eto, int32_t* active,
                           int32_t* result, uint32_t flags, void* stream);
+
+/* ---- the acquisition solve of a BO step (no reference counterpart: the reference's rollout solver
+ * is undefined, experiments/adaptive_bayesopt.jl:490; the specification is the build's host-driven
+ * loop, mrbo/bayesopt.py rollout_solve / rollout_solve_multi, and every output below is that loop's
+ * bit for bit -- tests/test_gpu_rollout_solve.py).  All three work on plain plans and surrogate
+ * batches; R is the plan's restarts per surrogate, the surrogate index is slowest.
+ *
+ * mrbo_box_adam_step: mrbo_adam_step with BoxAdam.update (mrbo/bayesopt.py) in place of Adam's: for
+ * every restart with active[r] ≠ 0 the eswavs test, then, over the plan's box [lb, ub], w = ub − lb,
+ *   u = (x − lb)/w,  g = ∇μx·w,  m ← β1·m + (1−β1)·g,  v ← β2·v + (1−β2)·g²,
+ *   u ← u + η·(m/(1−β1^t))/(√(v/(1−β2^t)) + ε),  x ← clip(lb + w·u, lb, ub)
+ * each operation rounded on its own; the clip by comparisons, so a NaN stays a NaN (numpy's clip).
+ * Device pointers only (eto R·S×W, x0s / m / v d×R·S, active int32 R·S); asynchronous on `stream`.
+ * MRBO_ERR_ARG, before any device call: a null argument, t < 1, a non-finite or negative eta, eps
+ * or sample_size, β outside [0, 1), any flag.                                                   */
+int mrbo_box_adam_step(mrbo_plan_t* plan, const double* eto, double* x0s, int32_t* active, double* m, double* v,
+                       int32_t t, double sample_size, double eta, double beta1, double beta2, double eps,
+                       uint32_t flags, void* stream);
+
+/* bayesopt.pick_restart per surrogate: among the R final points x[:, :, q] (x d×R×S) with ETO rows
+ * eto (R·S×W, only the means are read), the first one of the largest mean; means[r] is the mean, or
+ * −∞ where it is not finite.  With incumbent ≠ 0 a restart is novel when
+ *   min over the surrogate's N observed points X (the plan's device copy) of max_a |x_a − X_a|/w_a > 1e-9
+ * (a non-finite coordinate: not novel), and while any restart of the surrogate is novel the others
+ * rank −∞.  All ranks −∞: restart 0.  One workgroup per surrogate.
+ *   xnext d×S: the picked points;  mean S: their means;  pick int32 S: their indices in 0..R−1
+ *   means R×S or NULL
+ * Device pointers only; asynchronous on `stream`.  MRBO_ERR_ARG, before any device call: a null plan,
+ * x, eto, xnext, mean or pick, any flag.                                                       */
+int mrbo_pick_restart(mrbo_plan_t* plan, const double* x, const double* eto, int32_t incumbent, double* xnext,
+                      double* mean, int32_t* pick, double* means, uint32_t flags, void* stream);
+
+/* rollout_solve_multi in ONE call.  The inputs are staged once (MRBO_FLAG_HOST_POINTERS; else they
+ * are device pointers); then at most opts->iterations times [mrbo_simulate_mc with gradients at the
+ * current x0s, mrbo_eto_reduce, mrbo_sga_step / mrbo_adam_step / mrbo_box_adam_step, the check
+ * kernel] follow each other on the stream.  A restart that eswavs stops is skipped by the later
+ * launches; the host reads the number of active restarts two iterations behind the launches and
+ * ends the ascent once it is zero (the iterations queued meanwhile change nothing).  Unlike
+ * mrbo_stochastic_solve, status bits do NOT end the ascent -- the host loop goes on, and the NaN
+ * ETO rows of failed trajectories become −∞ means -- and the trajectory order is the plan's own.
+ * Then x0s is projected onto the plan's box in place (NaN kept), ONE launch with
+ * MRBO_FLAG_NO_GRADIENT evaluates every restart there (nothing skipped), mrbo_eto_reduce and
+ * mrbo_pick_restart(opts->incumbent) follow, and the stream is synchronised, once.
+ *   x0s      d×R×S in: the starts; out: the projected end points
+ *   rnstream, xstarts   as mrbo_simulate_mc
+ *   xnext, mean, pick, means   as mrbo_pick_restart (means may be NULL)
+ *   active   int32 R×S or NULL: 1 where eswavs never stopped the restart within the budget
+ *   result   HOST int32[4]: iterations launched; the iteration after which no restart was active
+ *            (or the iterations launched); the OR of the status bits of the ascent's launches; the
+ *            OR of the status bits of the final launch
+ * MRBO_ERR_ARG, before any device call: a null plan, x0s, rnstream, xstarts, opts, xnext, mean, pick
+ * or result; iterations < 1; an unknown optimizer; a non-finite or negative eta, eps or sample_size;
+ * β outside [0, 1); a flag other than MRBO_FLAG_HOST_POINTERS.  The plan's mrbo_kernel_times ring
+ * records every launch of the call.                                                            */
+typedef struct {
+  int32_t optimizer;    /* mrbo_optimizer_t: SGA, ADAM or BOX_ADAM                               */
+  int32_t iterations;   /* ≥ 1                                                                   */
+  double eta;           /* StandardSGA / Adam η; BOX_ADAM: box widths per step                   */
+  double beta1;         /* Adam, BoxAdam β1 (0.9); ignored by StandardSGA                        */
+  double beta2;         /* β2 (0.999)                                                            */
+  double eps;           /* ε (1e-8)                                                              */
+  double sample_size;   /* eswavs sample size (0 → the plan's M)                                 */
+  int32_t incumbent;    /* ≠ 0: never pick an observed point while another restart ends elsewhere */
+} mrbo_rollout_opts_t;
+int mrbo_rollout_solve(mrbo_plan_t* plan, double* x0s, const double* rnstream, const double* xstarts,
+                       const mrbo_rollout_opts_t* opts, double* xnext, double* mean, int32_t* pick, double* means,
+                       int32_t* active, int32_t* result, uint32_t flags, void* stream);
 
 /* Shard moments for the multi-GPU exchange: moments R×(2+2d+2) = [Σα, M2α, Σ∇x(d), M2∇x(d), Σ∇θ, M2∇θ]
  * over the first M_local samples of each restart (the outputs keep the plan's M as the restart

@@ -17,6 +17,7 @@
 #define MRBO_API_TU
 #include "mrbo_dispatch.h"
 #include "mrbo_mle.h"
+#include "mrbo_solve.h"
 #include "sobol_table.h"
 
 namespace mrbo {   // mrbo_order.hip
@@ -243,17 +244,7 @@ __global__ void __launch_bounds__(256) reduce_kernel(const double* values, const
 // eswavs (utils.jl:114-123) on the ETO's ∇μx and σ_∇μx -- stop when 1 − (M/d)·Σ_a ∇_a²/σ_a² > 0 (a
 // NaN ratio keeps iterating, as in Julia) -- else the optimizer's update! of x (StandardSGA
 // optimizers.jl:16-22 or Adam :49-74).  One thread per restart; the x0 batch and the Adam moments
-// never leave the device between launches.
-__device__ __forceinline__ bool eswavs_stops(const double* e, int d, double sample_size) {
-#pragma clang fp contract(off)   // the host mirror's (numpy) roundings: no fused multiply-adds
-  double ratio = 0.0;
-  for (int a = 0; a < d; ++a) {
-    const double g = e[2 + a], s = e[2 + d + a];
-    ratio += (g * g) / (s * s);
-  }
-  return 1.0 - (sample_size / d) * ratio > 0.0;
-}
-
+// never leave the device between launches.  eswavs_stops: mrbo_solve.h (shared with BoxAdam's step).
 __global__ void __launch_bounds__(64) sga_kernel(const double* eto, double* x0s, int* active, int R, int d,
                                                  double sample_size, double eta) {
 #pragma clang fp contract(off)
@@ -1283,6 +1274,191 @@ int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, c
   result[0] = it;                              // iterations launched
   result[1] = stopped_at ? stopped_at : it;    // the iteration after which no restart was active
   result[2] = bits;                            // OR of every launch's trajectory status bits
+  return MRBO_OK;
+}
+
+// the step options of Adam / BoxAdam and eswavs: finite and non-negative, β in [0, 1)
+static int check_step_opts(double sample_size, double eta, double beta1, double beta2, double eps) {
+  auto bad = [](double v) { return !std::isfinite(v) || v < 0.0; };
+  if (bad(eta)) return fail(MRBO_ERR_ARG, "eta=%g: finite and non-negative", eta);
+  if (bad(eps)) return fail(MRBO_ERR_ARG, "eps=%g: finite and non-negative", eps);
+  if (bad(sample_size)) return fail(MRBO_ERR_ARG, "sample_size=%g: finite and non-negative", sample_size);
+  if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(MRBO_ERR_ARG, "beta1=%g outside [0, 1)", beta1);
+  if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(MRBO_ERR_ARG, "beta2=%g outside [0, 1)", beta2);
+  return MRBO_OK;
+}
+
+int mrbo_box_adam_step(mrbo_plan_t* P, const double* eto, double* x0s, int32_t* active, double* m, double* v,
+                       int32_t t, double sample_size, double eta, double beta1, double beta2, double eps,
+                       uint32_t flags, void* stream) {
+  if (!P || !eto || !x0s || !active || !m || !v) return fail(MRBO_ERR_ARG, "null argument");
+  if (flags) return fail(MRBO_ERR_ARG, "flags: mrbo_box_adam_step takes device pointers and no flag");
+  if (t < 1) return fail(MRBO_ERR_ARG, "t=%d: the update count starts at 1", t);
+  if (int rc = check_step_opts(sample_size, eta, beta1, beta2, eps)) return rc;
+  if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
+  const double c1 = 1.0 - std::pow(beta1, (double)t), c2 = 1.0 - std::pow(beta2, (double)t);
+  launch_box_adam_step((hipStream_t)stream, eto, x0s, (int*)active, m, v, P->p.R * P->S, P->d, P->dlbs, P->dubs,
+                       sample_size, eta, beta1, beta2, eps, c1, c2);
+  HIP_TRY(hipGetLastError());
+  return MRBO_OK;
+}
+
+// mrbo_pick_restart on device pointers; means and novel are never null here
+static int pick_common(mrbo_plan_t* P, const double* x, const double* eto, int incumbent, double* xnext, double* mean,
+                       int32_t* pick, double* means, int* novel, hipStream_t st) {
+  PickParams q{};
+  q.d = P->d; q.N = P->N; q.R = P->p.R; q.S = P->S; q.ldX = P->NR; q.incumbent = incumbent != 0;
+  q.X0 = P->dX0; q.lbs = P->dlbs; q.ubs = P->dubs;
+  q.x = x; q.eto = eto; q.means = means; q.novel = novel; q.xnext = xnext; q.mean = mean; q.pick = (int*)pick;
+  launch_pick_restart(st, q);
+  HIP_TRY(hipGetLastError());
+  return MRBO_OK;
+}
+
+// slots of the plan's outer-ascent buffers (mrbo_plan::solve) that only the calls below use
+enum { SLOT_XNEXT = 14, SLOT_MEAN, SLOT_PICK, SLOT_MEANS, SLOT_NOVEL };
+
+int mrbo_pick_restart(mrbo_plan_t* P, const double* x, const double* eto, int32_t incumbent, double* xnext,
+                      double* mean, int32_t* pick, double* means, uint32_t flags, void* stream) {
+  if (!P || !x || !eto || !xnext || !mean || !pick) return fail(MRBO_ERR_ARG, "null argument");
+  if (flags) return fail(MRBO_ERR_ARG, "flags: mrbo_pick_restart takes device pointers and no flag");
+  if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
+  const size_t R = (size_t)P->p.R * P->S;
+  double* dmeans = means ? means : (double*)solve_slot(P, SLOT_MEANS, sizeof(double) * R);
+  int* dnovel = (int*)solve_slot(P, SLOT_NOVEL, sizeof(int) * R);
+  if (!dmeans || !dnovel) return fail(MRBO_ERR_NOMEM, "pick buffers");
+  return pick_common(P, x, eto, incumbent, xnext, mean, pick, dmeans, dnovel, (hipStream_t)stream);
+}
+
+int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, const double* xstarts,
+                       const mrbo_rollout_opts_t* o, double* xnext, double* mean, int32_t* pick, double* means,
+                       int32_t* active, int32_t* result, uint32_t flags, void* stream) {
+  if (!P || !x0s || !rnstream || !xstarts || !o || !xnext || !mean || !pick || !result)
+    return fail(MRBO_ERR_ARG, "null argument");
+  if (o->iterations < 1) return fail(MRBO_ERR_ARG, "iterations=%d: at least one", o->iterations);
+  if (o->optimizer != MRBO_OPT_SGA && o->optimizer != MRBO_OPT_ADAM && o->optimizer != MRBO_OPT_BOX_ADAM)
+    return fail(MRBO_ERR_ARG, "optimizer=%d unknown", o->optimizer);
+  if (int rc = check_step_opts(o->sample_size, o->eta, o->beta1, o->beta2, o->eps)) return rc;
+  if (flags & ~(uint32_t)MRBO_FLAG_HOST_POINTERS) return fail(MRBO_ERR_ARG, "flags: only MRBO_FLAG_HOST_POINTERS");
+  if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  const bool host = flags & MRBO_FLAG_HOST_POINTERS;
+  const bool moments = o->optimizer != MRBO_OPT_SGA;
+  const int d = P->d, M = P->p.M, R = P->p.R * P->S, S = P->S, h = P->p.h, W = 2 + 2 * d + 2;   // R·S restarts
+  const size_t T = (size_t)M * R;
+  const size_t nx = (size_t)d * R, nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
+  const double sample_size = o->sample_size > 0 ? o->sample_size : (double)M;
+  // device state, in mrbo_stochastic_solve's slots: x0, the inputs, the ETO rows, the stop flags, the
+  // launch outputs, the moments, the checks; then the pick's outputs
+  double* dx0 = host ? (double*)solve_slot(P, 0, sizeof(double) * nx) : x0s;
+  const double* drn = host ? (const double*)solve_slot(P, 1, sizeof(double) * nrn) : rnstream;
+  const double* dxs = host ? (const double*)solve_slot(P, 2, sizeof(double) * nxs) : xstarts;
+  double* deto = (double*)solve_slot(P, 4, sizeof(double) * R * W);
+  int32_t* dact = (host || !active) ? (int32_t*)solve_slot(P, 5, sizeof(int32_t) * R) : active;
+  double* dvals = (double*)solve_slot(P, 6, sizeof(double) * T);
+  double* dgx = (double*)solve_slot(P, 7, sizeof(double) * d * T);
+  double* dgt = (double*)solve_slot(P, 8, sizeof(double) * T);
+  int32_t* dst = (int32_t*)solve_slot(P, 9, sizeof(int32_t) * T);
+  double* dm = moments ? (double*)solve_slot(P, 10, sizeof(double) * nx) : nullptr;
+  double* dv = moments ? (double*)solve_slot(P, 11, sizeof(double) * nx) : nullptr;
+  int32_t* dchk = (int32_t*)solve_slot(P, 12, sizeof(int32_t) * 2 * mrbo_plan::NCHK);
+  double* dxn = host ? (double*)solve_slot(P, SLOT_XNEXT, sizeof(double) * d * S) : xnext;
+  double* dmean = host ? (double*)solve_slot(P, SLOT_MEAN, sizeof(double) * S) : mean;
+  int32_t* dpick = host ? (int32_t*)solve_slot(P, SLOT_PICK, sizeof(int32_t) * S) : pick;
+  double* dmeans = (host || !means) ? (double*)solve_slot(P, SLOT_MEANS, sizeof(double) * R) : means;
+  int* dnovel = (int*)solve_slot(P, SLOT_NOVEL, sizeof(int) * R);
+  if (!dx0 || !drn || !dxs || !deto || !dact || !dvals || !dgx || !dgt || !dst || !dchk || !dxn || !dmean || !dpick ||
+      !dmeans || !dnovel || (moments && (!dm || !dv)))
+    return fail(MRBO_ERR_NOMEM, "acquisition-solve buffers");
+  if (!P->hchk && hipHostMalloc(&P->hchk, sizeof(int32_t) * 2 * mrbo_plan::NCHK) != hipSuccess) {
+    P->hchk = nullptr;
+    return fail(MRBO_ERR_NOMEM, "pinned check ring");
+  }
+  for (auto& e : P->chk_ev)
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (host) {
+    HIP_TRY(hipMemcpyAsync(dx0, x0s, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)drn, rnstream, sizeof(double) * nrn, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)dxs, xstarts, sizeof(double) * nxs, hipMemcpyHostToDevice, st));
+  }
+  hipLaunchKernelGGL(fill_int_kernel, dim3((R + 63) / 64), dim3(64), 0, st, (int*)dact, R, 1);
+  if (moments) {
+    HIP_TRY(hipMemsetAsync(dm, 0, sizeof(double) * nx, st));
+    HIP_TRY(hipMemsetAsync(dv, 0, sizeof(double) * nx, st));
+  }
+  // The ascent, as mrbo_stochastic_solve runs it: iteration j's check (status bits, restarts still
+  // active) is read LAG iterations behind the launches, and a stopped restart is skipped by the
+  // later launches (kp.skip_active) -- its outputs and ETO row stay those of its last launch, which
+  // the host loop's relaunch reproduces bit for bit.  Status bits are collected, not acted on.
+  constexpr int LAG = 2;
+  int it = 0, stopped_at = 0, bits = 0;
+  auto read_check = [&](int j) -> int {   // iteration j ≥ 1 (its slot not yet reused)
+    const int k = (j - 1) % mrbo_plan::NCHK;
+    if (hipEventSynchronize(P->chk_ev[k]) != hipSuccess) return -1;
+    bits |= P->hchk[2 * k];
+    if (P->hchk[2 * k + 1] == 0 && !stopped_at) stopped_at = j;
+    return 0;
+  };
+  struct SkipGuard {
+    mrbo_plan_t* P;
+    ~SkipGuard() { P->skip_active = nullptr; }
+  } guard{P};
+  P->skip_active = dact;
+  int rc = MRBO_OK;
+  while (it < o->iterations && !stopped_at) {
+    ++it;
+    rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, dgx, dgt, dst, nullptr, nullptr, nullptr, 0, st);
+    if (rc != MRBO_OK) return rc;
+    rc = mrbo_eto_reduce(P, dvals, dgx, dgt, deto, 0, st);
+    if (rc != MRBO_OK) return rc;
+    if (o->optimizer == MRBO_OPT_SGA)
+      rc = mrbo_sga_step(P, deto, dx0, dact, sample_size, o->eta, 0, st);
+    else if (o->optimizer == MRBO_OPT_ADAM)
+      rc = mrbo_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
+    else
+      rc = mrbo_box_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
+    if (rc != MRBO_OK) return rc;
+    const int k = (it - 1) % mrbo_plan::NCHK;
+    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)T, (const int*)dact, R,
+                       (int*)dchk + 2 * k);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(P->hchk + 2 * k, dchk + 2 * k, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(P->chk_ev[k], st));
+    if (it > LAG && read_check(it - LAG)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
+  }
+  // rollout_solve's tail: the end points projected onto the box, one launch without gradients at
+  // them with nothing skipped, the ETO means, the pick.  Its check goes to the ring slot after the
+  // last iteration's: read long ago, and not one of the (at most LAG) checks still in flight.
+  P->skip_active = nullptr;
+  launch_box_project(st, dx0, (long long)nx, d, P->dlbs, P->dubs);
+  HIP_TRY(hipGetLastError());
+  rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, nullptr, nullptr, dst, nullptr, nullptr, nullptr,
+                        MRBO_FLAG_NO_GRADIENT, st);
+  if (rc != MRBO_OK) return rc;
+  rc = mrbo_eto_reduce(P, dvals, nullptr, nullptr, deto, 0, st);
+  if (rc != MRBO_OK) return rc;
+  rc = pick_common(P, dx0, deto, o->incumbent, dxn, dmean, dpick, dmeans, dnovel, st);
+  if (rc != MRBO_OK) return rc;
+  const int kf = it % mrbo_plan::NCHK;
+  hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)T, (const int*)dact, R,
+                     (int*)dchk + 2 * kf);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(P->hchk + 2 * kf, dchk + 2 * kf, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+  if (host) {
+    HIP_TRY(hipMemcpyAsync(x0s, dx0, sizeof(double) * nx, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(xnext, dxn, sizeof(double) * d * S, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mean, dmean, sizeof(double) * S, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pick, dpick, sizeof(int32_t) * S, hipMemcpyDeviceToHost, st));
+    if (means) HIP_TRY(hipMemcpyAsync(means, dmeans, sizeof(double) * R, hipMemcpyDeviceToHost, st));
+    if (active) HIP_TRY(hipMemcpyAsync(active, dact, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // the call's one synchronisation (the lagged reads aside)
+  for (int j = std::max(1, it - LAG + 1); j <= it; ++j)   // the last checks: complete by now
+    if (read_check(j)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
+  result[0] = it;                              // iterations launched
+  result[1] = stopped_at ? stopped_at : it;    // the iteration after which no restart was active
+  result[2] = bits;                            // OR of the status bits of the ascent's launches
+  result[3] = P->hchk[2 * kf];                 // ... of the final launch
   return MRBO_OK;
 }
 

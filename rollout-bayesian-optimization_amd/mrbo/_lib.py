@@ -37,9 +37,10 @@ EXPORTS = [
     "mrbo_plan_info", "mrbo_last_gp_fit_ms", "mrbo_plan_set_order", "mrbo_base_solve", "mrbo_sga_step",
     "mrbo_kernel_times", "mrbo_merge_moments", "mrbo_adam_step", "mrbo_stochastic_solve",
     "mrbo_plan_order_longest_first", "mrbo_plan_create_batch", "mrbo_gp_fit_multi", "mrbo_gp_optimize_multi",
+    "mrbo_box_adam_step", "mrbo_pick_restart", "mrbo_rollout_solve",
 ]
 
-MRBO_OPT_SGA, MRBO_OPT_ADAM = 0, 1
+MRBO_OPT_SGA, MRBO_OPT_ADAM, MRBO_OPT_BOX_ADAM = 0, 1, 2
 
 
 class SurrogateDesc(ctypes.Structure):
@@ -63,6 +64,13 @@ class SolveOpts(ctypes.Structure):
     _fields_ = [("optimizer", ctypes.c_int32), ("iterations", ctypes.c_int32), ("eta", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
                 ("sample_size", ctypes.c_double)]
+
+
+class RolloutOpts(ctypes.Structure):
+    """mrbo_rollout_opts_t (include/mrbo.h)."""
+    _fields_ = [("optimizer", ctypes.c_int32), ("iterations", ctypes.c_int32), ("eta", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("sample_size", ctypes.c_double), ("incumbent", ctypes.c_int32)]
 
 
 class MleOpts(ctypes.Structure):
@@ -111,6 +119,10 @@ def load():
         ctypes.c_uint32, _vp]
     L.mrbo_stochastic_solve.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(SolveOpts), _vp, _vp,
                                         ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
+    L.mrbo_box_adam_step.argtypes = L.mrbo_adam_step.argtypes
+    L.mrbo_pick_restart.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
+    L.mrbo_rollout_solve.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(RolloutOpts), _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
     L.mrbo_base_solve.argtypes = [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
     L.mrbo_rnstream.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp]
     L.mrbo_initial_guesses.argtypes = [ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp]

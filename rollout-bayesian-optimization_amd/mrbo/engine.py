@@ -247,6 +247,93 @@ class RolloutPlan:
                                                   ctypes.c_void_p(st.cuda_stream)))
         return int(res[0]), int(res[1]), int(res[2])
 
+    def box_adam_step(self, eto, x0s, active, m, v, t, sample_size, eta=0.02, beta1=0.9, beta2=0.999, eps=1e-8,
+                      stream=None):
+        """mrbo_box_adam_step: eswavs + BoxAdam.update (mrbo/bayesopt.py) over the plan's box for every
+        active restart, in place on the device tensors of adam_step."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        p = lambda t_: ctypes.c_void_p(t_.data_ptr())
+        _lib.check(self.lib.mrbo_box_adam_step(self.handle, p(eto), p(x0s), p(active), p(m), p(v), int(t),
+                                               float(sample_size), float(eta), float(beta1), float(beta2),
+                                               float(eps), 0, ctypes.c_void_p(st.cuda_stream)))
+
+    def pick_restart(self, x, eto, incumbent=True, means=None, stream=None):
+        """mrbo_pick_restart on device tensors: x (d·R·S, column-major), eto from `eto()`; means (R·S)
+        receives the restarts' means when given.  Returns the device tensors (xnext d·S, mean S,
+        pick int32 S); asynchronous."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = f"cuda:{self.device}"
+        xnext = torch.empty(self.d * self.S, dtype=torch.float64, device=dev)
+        mean = torch.empty(self.S, dtype=torch.float64, device=dev)
+        pick = torch.empty(self.S, dtype=torch.int32, device=dev)
+        p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())
+        _lib.check(self.lib.mrbo_pick_restart(self.handle, p(x), p(eto), int(bool(incumbent)), p(xnext), p(mean),
+                                              p(pick), p(means), 0, ctypes.c_void_p(st.cuda_stream)))
+        return xnext, mean, pick
+
+    OPTIMIZERS = {"sga": _lib.MRBO_OPT_SGA, "adam": _lib.MRBO_OPT_ADAM, "box_adam": _lib.MRBO_OPT_BOX_ADAM}
+
+    def _rollout_opts(self, optimizer, iterations, eta, beta1, beta2, eps, sample_size, incumbent):
+        opt = self.OPTIMIZERS[optimizer]
+        eta = {"sga": 0.01, "adam": 0.001, "box_adam": 0.02}[optimizer] if eta is None else eta
+        return _lib.RolloutOpts(opt, int(iterations), float(eta), float(beta1), float(beta2), float(eps),
+                                float(sample_size), int(bool(incumbent)))
+
+    def rollout_solve(self, x0s, rnstream, xstarts, optimizer="sga", iterations=50, eta=None, beta1=0.9, beta2=0.999,
+                      eps=1e-8, sample_size=0, incumbent=True, means=None, active=None, stream=None):
+        """mrbo_rollout_solve on device tensors: the whole acquisition solve of a BO step -- the ascent
+        of the plan's R·S restarts ("sga", "adam" or "box_adam"), the projection of x0s (d·R·S,
+        column-major, updated in place) onto the box, the final evaluation and the pick -- in one
+        call.  means (R·S) and active (R·S, int32) receive the final means and stop flags when given.
+        Returns (xnext d·S, mean S, pick int32 S) as device tensors and the call's result (iterations
+        launched, iteration after which no restart was active, status bits of the ascent, of the final
+        launch); the stream is synchronised."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = f"cuda:{self.device}"
+        xnext = torch.empty(self.d * self.S, dtype=torch.float64, device=dev)
+        mean = torch.empty(self.S, dtype=torch.float64, device=dev)
+        pick = torch.empty(self.S, dtype=torch.int32, device=dev)
+        p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())
+        o = self._rollout_opts(optimizer, iterations, eta, beta1, beta2, eps, sample_size, incumbent)
+        res = (ctypes.c_int32 * 4)()
+        _lib.check(self.lib.mrbo_rollout_solve(self.handle, p(x0s), p(rnstream), p(xstarts), ctypes.byref(o), p(xnext),
+                                               p(mean), p(pick), p(means), p(active), res, 0,
+                                               ctypes.c_void_p(st.cuda_stream)))
+        return xnext, mean, pick, tuple(int(r) for r in res)
+
+    def rollout_solve_host(self, x0s, rnstream, xstarts, optimizer="sga", iterations=50, eta=None, beta1=0.9,
+                           beta2=0.999, eps=1e-8, sample_size=0, incumbent=True, stream=None):
+        """rollout_solve on numpy arrays (MRBO_FLAG_HOST_POINTERS: the library stages them once): x0s
+        d×R×S (d×R on a plain plan), rnstream M×(d+1)×(h+1), xstarts d×nstarts.  Returns a dict of
+        numpy arrays -- x (the projected end points, x0s's shape), xnext d×S, mean S, pick S, means
+        R×S, active R×S -- and `result` as rollout_solve."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        d, R, S = self.d, self.R, self.S
+        shape = np.shape(x0s)
+        if shape not in ((d, R, S), (d, R * S)):
+            raise ValueError(f"x0s must be d×R×S = {(d, R, S)}; got {shape}")
+        x = np.asarray(x0s, dtype=np.float64).ravel(order="F").copy()
+        rn = np.asarray(rnstream, dtype=np.float64).ravel(order="F")
+        xs = np.asarray(xstarts, dtype=np.float64).ravel(order="F")
+        if rn.size != self.M * (d + 1) * (self.h + 1) or xs.size != d * self.nstarts:
+            raise ValueError(f"rnstream has {rn.size} entries, xstarts {xs.size}; the plan has M = {self.M}, "
+                             f"h = {self.h}, {self.nstarts} inner starts")
+        xnext, mean, means = np.empty(d * S), np.empty(S), np.empty(R * S)
+        pick, active = np.empty(S, dtype=np.int32), np.empty(R * S, dtype=np.int32)
+        p = lambda a: ctypes.c_void_p(a.ctypes.data)
+        o = self._rollout_opts(optimizer, iterations, eta, beta1, beta2, eps, sample_size, incumbent)
+        res = (ctypes.c_int32 * 4)()
+        _lib.check(self.lib.mrbo_rollout_solve(self.handle, p(x), p(rn), p(xs), ctypes.byref(o), p(xnext), p(mean),
+                                               p(pick), p(means), p(active), res, _lib.MRBO_FLAG_HOST_POINTERS,
+                                               ctypes.c_void_p(st.cuda_stream)))
+        return dict(x=x.reshape(shape, order="F"), xnext=xnext.reshape((d, S), order="F"), mean=mean, pick=pick,
+                    means=means.reshape((R, S), order="F"), active=active.reshape((R, S), order="F"),
+                    result=tuple(int(r) for r in res))
+
     def eval_base(self, xs):
         """eval(s, x, θ) at the columns of xs (d×P); returns (3+4d+d²)×P numpy -- on a surrogate
         batch (S > 1) the S blocks, (3+4d+d²)×P×S."""
