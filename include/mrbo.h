@@ -14,6 +14,8 @@
  *                          over a restart batch, the whole ascent in one call
  *   mrbo_rollout_solve     the build's acquisition solve of a BO step (the reference's rollout solver
  *                          is undefined): the ascent, the final evaluation and the pick in one call
+ *   mrbo_simulate_control, mrbo_eto_reduce_cv   the build's EI control variate (the reference's
+ *                          --variance-reduction names an undefined solver): variance-reduced ETO rows
  *   mrbo_eval_base         eval(s::Surrogate, x, θ) radial_basis_surrogates.jl:224-310 (μ, σ, ∇, Hα)
  *   mrbo_rnstream          gen_low_discrepancy_sequence utils.jl:65-74 (Sobol→Box–Muller(log10))
  *   mrbo_initial_guesses   generate_initial_guesses utils.jl:145-153
@@ -341,6 +343,52 @@ int mrbo_rollout_solve(mrbo_plan_t* plan, double* x0s, const double* rnstream, c
                        const mrbo_rollout_opts_t* opts, double* xnext, double* mean, int32_t* pick, double* means,
                        int32_t* active, int32_t* result, uint32_t flags, void* stream);
 
+/* ---- the EI control variate: variance-reduced ETO rows (the reference's --variance-reduction, "Use EI
+ * as a control variate for variance reduction", experiments/nonmyopic_bayesopt.jl:64-66, ends in an
+ * undefined solver; the definition is the build's, DESIGN.md §16, its specification mrbo/variance.py).
+ * A trajectory's value is v = max(fmini − min_k y_k, 0); its step-0 part c = max(fmini − y_0, 0) is the
+ * value of the same trajectory cut at horizon 0, with E[c] = EI0(x0) = σ·(u·Φ(u) + φ(u)) and
+ * E[∇c] = φ(u)·∇σ − Φ(u)·∇μ, u = (fmini − μ)/σ, whatever the plan's rule, θ and cost model are.
+ *
+ * mrbo_simulate_control: the plan's own rollout launch run to horizon 0 on a plan of any h -- the
+ * control samples of the trajectories mrbo_simulate_mc runs from the same x0s and rnstream (only the
+ * stream's step-0 slab, its first M×(d+1) block, is read; a host stream is staged to that length).
+ *   values0 M×R, grad_x0 d×M×R (may be NULL with MRBO_FLAG_NO_GRADIENT), status0 M×R
+ * Bit-identical to mrbo_simulate_mc on a plan created with h = 0.  It honours the plan's order and a
+ * solve's skipping of stopped restarts, and takes one entry of the timing ring.  Flags:
+ * MRBO_FLAG_HOST_POINTERS, MRBO_FLAG_NO_GRADIENT; any other flag, a null plan or array: MRBO_ERR_ARG
+ * before any device call.  Launches on `stream` without synchronising (device pointers).           */
+int mrbo_simulate_control(mrbo_plan_t* plan, const double* x0s, const double* rnstream, const double* xstarts,
+                          double* values0, double* grad_x0, int32_t* status0, uint32_t flags, void* stream);
+
+/* mrbo_eto_reduce with the control variate.  Per restart and per series a -- the value and each
+ * component of ∇x -- with target a_m (values / grad_x), control b_m (values0 / grad_x0) and the
+ * control's expectation e:  ā = Σa/M, b̄ = Σb/M, da = a − ā, db = b − b̄, Sbb = Σdb², Sab = Σda·db,
+ *   β = Sab/Sbb if Sbb > 0 and both sums are finite, else 0
+ *   β ≠ 0:  mean = ā − β·(b̄ − e),  std = sqrt(Σ(da − β·db)²/(M − 1))
+ *   β = 0:  the entries of mrbo_eto_reduce, bit for bit; e is not read (it may be NaN)
+ * The ∇θ columns are always mrbo_eto_reduce's (the control does not depend on θ).  e comes from the
+ * plan's base evaluation (the kernel of mrbo_eval_base) at x0s, launched by this call into a
+ * plan-owned buffer (grown on first use), and the plan's fmini per surrogate.
+ *   x0s d×R·S; values, grad_x, grad_theta as mrbo_eto_reduce (grad_x == NULL: value columns only, the
+ *   gradient columns as mrbo_eto_reduce writes them and β_a = 0); values0, grad_x0 from
+ *   mrbo_simulate_control at the same x0s; eto R·S×W in mrbo_eto_reduce's layout; beta (1+d)×R·S
+ *   column-major [value, ∇x (d)] per restart, or NULL
+ * Device pointers only; asynchronous on `stream`.  MRBO_ERR_ARG, before any device call: a null plan,
+ * x0s, values, values0 or eto, grad_x without grad_x0, any flag.                                  */
+int mrbo_eto_reduce_cv(mrbo_plan_t* plan, const double* x0s, const double* values, const double* grad_x,
+                       const double* grad_theta, const double* values0, const double* grad_x0, double* eto,
+                       double* beta, uint32_t flags, void* stream);
+
+/* The switch (default off).  On: mrbo_rollout_solve runs, per iteration, [mrbo_simulate_mc,
+ * mrbo_simulate_control, mrbo_eto_reduce_cv, the step, the check], and its tail the same two launches
+ * without gradients before mrbo_pick_restart; stopped restarts are skipped in both launches; result[2]
+ * and result[3] OR the status bits of both; the timing ring records both.  mrbo_stochastic_solve --
+ * the reference's stochastic_solve, which has no control variate -- returns MRBO_ERR_UNSUPPORTED
+ * before any device call.  mrbo_eto_reduce, the moments calls and mrbo_simulate_* ignore the switch,
+ * and with it off every output of every call keeps its bits.  A null plan: MRBO_ERR_ARG.          */
+int mrbo_plan_set_control_variate(mrbo_plan_t* plan, int32_t on);
+
 /* Shard moments for the multi-GPU exchange: moments R×(2+2d+2) = [Σα, M2α, Σ∇x(d), M2∇x(d), Σ∇θ, M2∇θ]
  * over the first M_local samples of each restart (the outputs keep the plan's M as the restart
  * stride; 1 ≤ M_local ≤ M), M2 = Σ(x − x̄_local)² by two passes.  Ranks all-gather
@@ -458,7 +506,8 @@ int mrbo_initial_guesses(int32_t n, int32_t d, const double* lbs, const double* 
 double mrbo_dual_uniform(uint64_t seed, int64_t traj, int32_t j, int32_t k);
 
 /* Timing of the last mrbo_simulate_mc / _ghq rollout kernel on its stream (HIP events around the
- * kernel launch alone), milliseconds; -1 before the first launch.  Waits for that launch.      */
+ * kernel launch alone), milliseconds; -1 before the first launch.  Waits for that launch.
+ * mrbo_simulate_control is such a launch too: it takes one entry of the ring.                  */
 double mrbo_last_kernel_ms(mrbo_plan_t* plan);
 
 /* The same for the plan's last min(n, launches, 64) launches, oldest first, into ms[]; returns the

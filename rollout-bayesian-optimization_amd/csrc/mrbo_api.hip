@@ -18,6 +18,7 @@
 #include "mrbo_dispatch.h"
 #include "mrbo_mle.h"
 #include "mrbo_solve.h"
+#include "mrbo_cv.h"
 #include "sobol_table.h"
 
 namespace mrbo {   // mrbo_order.hip
@@ -80,6 +81,7 @@ struct mrbo_plan {
   void* oorder = nullptr;           // mrbo_plan_order_longest_first: keys, ranking, sort scratch, order
   size_t oorder_bytes = 0;
   const int32_t* skip_active = nullptr;   // set by mrbo_stochastic_solve for its launches only
+  int control_variate = 0;  // mrbo_plan_set_control_variate: mrbo_rollout_solve's rows are mrbo_eto_reduce_cv's
   int wpg = 4, blocks = 0;
   size_t smem = 0;
   int spec = 0;             // 1: rollout_kernel<D, RPL, 1> (Matérn-5/2 + EI fixed); 2: its half-wave form <D, 1, 1, 2>;
@@ -885,22 +887,25 @@ int mrbo_plan_destroy(mrbo_plan_t* P) {
 }
 
 // one launch of the rollout kernel: Monte-Carlo draws from rnstream, or the Gauss–Hermite
-// observable from (ghq_nodes, ghq_w) when those are given
+// observable from (ghq_nodes, ghq_w) when those are given.  hz < 0: the plan's horizon; hz ≥ 0
+// (mrbo_simulate_control: 0) runs the trajectories to horizon hz ≤ the plan's instead -- the kernel
+// reads the horizon at run time, the sizes of the staged arrays follow it, and ∇θ is optional
 static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnstream, const double* ghq_nodes,
                            const double* ghq_w, const double* xstarts, const double* dual_y_dx,
                            const double* replay_x, double* values, double* grad_x, double* grad_theta,
                            int32_t* status, double* policy_x, double* obs, int64_t* evals, uint32_t flags,
-                           void* stream) {
+                           void* stream, int hz = -1) {
   if (!P || !x0s || !(rnstream || (ghq_nodes && ghq_w)) || !xstarts || !values || !status)
     return fail(MRBO_ERR_ARG, "null argument");
   const bool with_grad = !(flags & MRBO_FLAG_NO_GRADIENT);
-  if (with_grad && (!grad_x || !grad_theta)) return fail(MRBO_ERR_ARG, "gradient containers required");
+  if (with_grad && (!grad_x || (!grad_theta && hz < 0))) return fail(MRBO_ERR_ARG, "gradient containers required");
   hipStream_t st = (hipStream_t)stream;
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
-  const int d = P->d, h = P->p.h, M = P->p.M, R = P->p.R * P->S, S = P->S;
+  const int d = P->d, h = hz < 0 ? P->p.h : std::min(hz, (int)P->p.h), M = P->p.M, R = P->p.R * P->S, S = P->S;
   const size_t T = (size_t)M * R;   // over all S surrogates: the sizes of the staged arrays
   KParams kp;
   fill_common(P, kp);
+  kp.h = h;
   kp.with_gradient = with_grad ? 1 : 0;
   kp.T = (long long)(T / S);        // the kernel's trajectory range: ONE surrogate's M×R
   Stage sg(P);
@@ -1051,7 +1056,7 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
     HIP_TRY(hipMemcpy(status, dstatus, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
     if (with_grad) {
       HIP_TRY(hipMemcpy(grad_x, dgx, sizeof(double) * d * T, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(grad_theta, dgt, sizeof(double) * T, hipMemcpyDeviceToHost));
+      if (grad_theta) HIP_TRY(hipMemcpy(grad_theta, dgt, sizeof(double) * T, hipMemcpyDeviceToHost));
     }
     if (policy_x) HIP_TRY(hipMemcpy(policy_x, dpol, sizeof(double) * d * (h + 1) * T, hipMemcpyDeviceToHost));
     if (obs) HIP_TRY(hipMemcpy(obs, dobs, sizeof(double) * (h + 1) * T, hipMemcpyDeviceToHost));
@@ -1162,6 +1167,8 @@ int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, c
   if (o->optimizer != MRBO_OPT_SGA && o->optimizer != MRBO_OPT_ADAM)
     return fail(MRBO_ERR_ARG, "optimizer=%d unknown", o->optimizer);
   if (flags & ~(uint32_t)MRBO_FLAG_HOST_POINTERS) return fail(MRBO_ERR_ARG, "flags: only MRBO_FLAG_HOST_POINTERS");
+  if (P->control_variate)   // the reference's stochastic_solve has no control variate (mrbo_rollout_solve does)
+    return fail(MRBO_ERR_UNSUPPORTED, "mrbo_stochastic_solve on a plan with the control variate switched on");
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   hipStream_t st = (hipStream_t)stream;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
@@ -1316,7 +1323,7 @@ static int pick_common(mrbo_plan_t* P, const double* x, const double* eto, int i
 }
 
 // slots of the plan's outer-ascent buffers (mrbo_plan::solve) that only the calls below use
-enum { SLOT_XNEXT = 14, SLOT_MEAN, SLOT_PICK, SLOT_MEANS, SLOT_NOVEL };
+enum { SLOT_XNEXT = 14, SLOT_MEAN, SLOT_PICK, SLOT_MEANS, SLOT_NOVEL, SLOT_CV_BASE, SLOT_CV_VALUES, SLOT_CV_GRAD };
 
 int mrbo_pick_restart(mrbo_plan_t* P, const double* x, const double* eto, int32_t incumbent, double* xnext,
                       double* mean, int32_t* pick, double* means, uint32_t flags, void* stream) {
@@ -1358,7 +1365,14 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
   double* dvals = (double*)solve_slot(P, 6, sizeof(double) * T);
   double* dgx = (double*)solve_slot(P, 7, sizeof(double) * d * T);
   double* dgt = (double*)solve_slot(P, 8, sizeof(double) * T);
-  int32_t* dst = (int32_t*)solve_slot(P, 9, sizeof(int32_t) * T);
+  // with the control variate (mrbo_plan_set_control_variate) every rollout launch is followed by its
+  // horizon-0 control launch: its status words stand behind the rollout's, so that one check reads both
+  const bool cv = P->control_variate != 0;
+  const size_t nst = cv ? 2 * T : T;
+  int32_t* dst = (int32_t*)solve_slot(P, 9, sizeof(int32_t) * nst);
+  double* dv0 = cv ? (double*)solve_slot(P, SLOT_CV_VALUES, sizeof(double) * T) : nullptr;
+  double* dg0 = cv ? (double*)solve_slot(P, SLOT_CV_GRAD, sizeof(double) * d * T) : nullptr;
+  if (cv && (!dv0 || !dg0)) return fail(MRBO_ERR_NOMEM, "control-variate buffers");
   double* dm = moments ? (double*)solve_slot(P, 10, sizeof(double) * nx) : nullptr;
   double* dv = moments ? (double*)solve_slot(P, 11, sizeof(double) * nx) : nullptr;
   int32_t* dchk = (int32_t*)solve_slot(P, 12, sizeof(int32_t) * 2 * mrbo_plan::NCHK);
@@ -1409,7 +1423,13 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
     ++it;
     rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, dgx, dgt, dst, nullptr, nullptr, nullptr, 0, st);
     if (rc != MRBO_OK) return rc;
-    rc = mrbo_eto_reduce(P, dvals, dgx, dgt, deto, 0, st);
+    if (cv) {   // the control launch skips the stopped restarts too; their rows keep their bits
+      rc = mrbo_simulate_control(P, dx0, drn, dxs, dv0, dg0, dst + T, 0, st);
+      if (rc != MRBO_OK) return rc;
+      rc = mrbo_eto_reduce_cv(P, dx0, dvals, dgx, dgt, dv0, dg0, deto, nullptr, 0, st);
+    } else {
+      rc = mrbo_eto_reduce(P, dvals, dgx, dgt, deto, 0, st);
+    }
     if (rc != MRBO_OK) return rc;
     if (o->optimizer == MRBO_OPT_SGA)
       rc = mrbo_sga_step(P, deto, dx0, dact, sample_size, o->eta, 0, st);
@@ -1419,8 +1439,8 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
       rc = mrbo_box_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
     if (rc != MRBO_OK) return rc;
     const int k = (it - 1) % mrbo_plan::NCHK;
-    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)T, (const int*)dact, R,
-                       (int*)dchk + 2 * k);
+    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)nst, (const int*)dact,
+                       R, (int*)dchk + 2 * k);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(P->hchk + 2 * k, dchk + 2 * k, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(P->chk_ev[k], st));
@@ -1435,12 +1455,18 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
   rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, nullptr, nullptr, dst, nullptr, nullptr, nullptr,
                         MRBO_FLAG_NO_GRADIENT, st);
   if (rc != MRBO_OK) return rc;
-  rc = mrbo_eto_reduce(P, dvals, nullptr, nullptr, deto, 0, st);
+  if (cv) {   // the means the pick ranks are the control-variate ones as well
+    rc = mrbo_simulate_control(P, dx0, drn, dxs, dv0, nullptr, dst + T, MRBO_FLAG_NO_GRADIENT, st);
+    if (rc != MRBO_OK) return rc;
+    rc = mrbo_eto_reduce_cv(P, dx0, dvals, nullptr, nullptr, dv0, nullptr, deto, nullptr, 0, st);
+  } else {
+    rc = mrbo_eto_reduce(P, dvals, nullptr, nullptr, deto, 0, st);
+  }
   if (rc != MRBO_OK) return rc;
   rc = pick_common(P, dx0, deto, o->incumbent, dxn, dmean, dpick, dmeans, dnovel, st);
   if (rc != MRBO_OK) return rc;
   const int kf = it % mrbo_plan::NCHK;
-  hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)T, (const int*)dact, R,
+  hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)nst, (const int*)dact, R,
                      (int*)dchk + 2 * kf);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(P->hchk + 2 * kf, dchk + 2 * kf, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
@@ -1489,6 +1515,48 @@ int mrbo_eval_base(mrbo_plan_t* P, int32_t npts, const double* xs, double* out, 
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(out, dout, sizeof(double) * stride * npts * S, hipMemcpyDeviceToHost));
   }
+  return MRBO_OK;
+}
+
+// ---- the EI control variate -------------------------------------------------------
+int mrbo_plan_set_control_variate(mrbo_plan_t* P, int32_t on) {
+  if (!P) return fail(MRBO_ERR_ARG, "null plan");
+  P->control_variate = on != 0;
+  return MRBO_OK;
+}
+
+int mrbo_simulate_control(mrbo_plan_t* P, const double* x0s, const double* rnstream, const double* xstarts,
+                          double* values0, double* grad_x0, int32_t* status0, uint32_t flags, void* stream) {
+  if (!P || !x0s || !rnstream || !xstarts || !values0 || !status0) return fail(MRBO_ERR_ARG, "null argument");
+  if (flags & ~(uint32_t)(MRBO_FLAG_HOST_POINTERS | MRBO_FLAG_NO_GRADIENT))
+    return fail(MRBO_ERR_ARG, "flags: only MRBO_FLAG_HOST_POINTERS and MRBO_FLAG_NO_GRADIENT");
+  if (!(flags & MRBO_FLAG_NO_GRADIENT) && !grad_x0) return fail(MRBO_ERR_ARG, "null grad_x0 without MRBO_FLAG_NO_GRADIENT");
+  // the plan's own rollout launch with the horizon at 0: no inner solve, no adjoint, ∇θ = 0 unwritten
+  return simulate_common(P, x0s, rnstream, nullptr, nullptr, xstarts, nullptr, nullptr, values0, grad_x0, nullptr,
+                         status0, nullptr, nullptr, nullptr, flags, stream, 0);
+}
+
+int mrbo_eto_reduce_cv(mrbo_plan_t* P, const double* x0s, const double* values, const double* grad_x,
+                       const double* grad_theta, const double* values0, const double* grad_x0, double* eto,
+                       double* beta, uint32_t flags, void* stream) {
+  if (!P || !x0s || !values || !values0 || !eto) return fail(MRBO_ERR_ARG, "null argument");
+  if (grad_x && !grad_x0) return fail(MRBO_ERR_ARG, "null grad_x0 with gradients");
+  if (flags) return fail(MRBO_ERR_ARG, "flags: mrbo_eto_reduce_cv takes device pointers and no flag");
+  hipStream_t st = (hipStream_t)stream;
+  const int d = P->d, R = P->p.R, S = P->S;
+  // μ, σ, ∇μ, ∇σ at the R·S points x0 by the plan's base evaluation, into a plan-owned buffer: on a
+  // surrogate batch all points on every surrogate in one launch, restart r of surrogate q reading
+  // point q·R + r of block q (the S-fold surplus is noise beside a rollout launch)
+  const size_t stride = 3 + 4 * (size_t)d + (size_t)d * d;
+  double* dbase = (double*)solve_slot(P, SLOT_CV_BASE, sizeof(double) * stride * R * S * S);
+  if (!dbase) return fail(MRBO_ERR_NOMEM, "control-variate base evaluation");
+  if (int rc = mrbo_eval_base(P, R * S, x0s, dbase, 0, stream)) return rc;
+  CvParams q{};
+  q.d = d; q.M = P->p.M; q.R = R; q.S = S;
+  q.values = values; q.grad_x = grad_x; q.grad_theta = grad_theta; q.values0 = values0; q.grad_x0 = grad_x0;
+  q.base = dbase; q.stab = P->dstab; q.fmini = P->fmini; q.eto = eto; q.beta = beta;
+  launch_cv_reduce(st, q);
+  HIP_TRY(hipGetLastError());
   return MRBO_OK;
 }
 

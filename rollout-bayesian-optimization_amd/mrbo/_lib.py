@@ -38,6 +38,7 @@ EXPORTS = [
     "mrbo_kernel_times", "mrbo_merge_moments", "mrbo_adam_step", "mrbo_stochastic_solve",
     "mrbo_plan_order_longest_first", "mrbo_plan_create_batch", "mrbo_gp_fit_multi", "mrbo_gp_optimize_multi",
     "mrbo_box_adam_step", "mrbo_pick_restart", "mrbo_rollout_solve",
+    "mrbo_simulate_control", "mrbo_eto_reduce_cv", "mrbo_plan_set_control_variate",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM, MRBO_OPT_BOX_ADAM = 0, 1, 2
@@ -123,6 +124,9 @@ def load():
     L.mrbo_pick_restart.argtypes = [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
     L.mrbo_rollout_solve.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(RolloutOpts), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
+    L.mrbo_simulate_control.argtypes = [_vp] + [_vp] * 6 + [ctypes.c_uint32, _vp]
+    L.mrbo_eto_reduce_cv.argtypes = [_vp] + [_vp] * 8 + [ctypes.c_uint32, _vp]
+    L.mrbo_plan_set_control_variate.argtypes = [_vp, ctypes.c_int32]
     L.mrbo_base_solve.argtypes = [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
     L.mrbo_rnstream.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp]
     L.mrbo_initial_guesses.argtypes = [ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp]

@@ -117,17 +117,25 @@ def incumbent_start(sur, lbs, ubs):
     return np.clip(xb + step, lbs, ubs)
 
 
-def _device_solve(plan, x0, tp, es, sgd_iterations, eta, solver, incumbent):
+def _device_solve(plan, x0, tp, es, sgd_iterations, eta, solver, incumbent, variance_reduction=False):
     """The acquisition solve as ONE library call (mrbo_rollout_solve) on the plan the host loop would
     use: the ascent from x0 (StandardSGA, or BoxAdam with Adam's default β1, β2, ε), the projection
-    onto the box, the final evaluation and pick_restart.  Every output equals the host loop's."""
-    return plan.rollout_solve_host(x0, tp.rnstream_sequence, es.get_starts(),
-                                   optimizer="sga" if solver == "sga" else "box_adam", iterations=sgd_iterations,
-                                   eta=eta, sample_size=tp.mc_iters, incumbent=incumbent)
+    onto the box, the final evaluation and pick_restart.  Every output equals the host loop's.
+    variance_reduction sets the plan's control-variate switch for the call and clears it afterwards
+    (the plan is cached and shared with the calls that leave it off)."""
+    if variance_reduction:
+        plan.set_control_variate(True)
+    try:
+        return plan.rollout_solve_host(x0, tp.rnstream_sequence, es.get_starts(),
+                                       optimizer="sga" if solver == "sga" else "box_adam", iterations=sgd_iterations,
+                                       eta=eta, sample_size=tp.mc_iters, incumbent=incumbent)
+    finally:
+        if variance_reduction:
+            plan.set_control_variate(False)
 
 
 def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta, eta=0.01,
-                  device=0, solver="sga", incumbent=True, trace=None, device_solve=False):
+                  device=0, solver="sga", incumbent=True, trace=None, device_solve=False, variance_reduction=False):
     """xnext from the rollout acquisition: restarts from a Sobol batch (StandardSGA with step `eta`,
     or BoxAdam with `eta` box widths per step), best final ETO mean.
 
@@ -139,7 +147,10 @@ def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_it
     restart and the loop re-observes it for the rest of the budget.
     `trace`, a list, receives one dict per call (batch, final points, final ETO means, pick).
     device_solve=True runs the ascent, the final evaluation and the pick as one device-resident call
-    (mrbo_rollout_solve) with the same results; the default keeps the host-driven loop."""
+    (mrbo_rollout_solve) with the same results; the default keeps the host-driven loop.
+    variance_reduction=True (the reference's --variance-reduction): every ETO row of the ascent and
+    the final means use EI0 at the restart's point as a control variate (mrbo/variance.py, DESIGN.md
+    §16), on either path with the same results."""
     lbs, ubs = np.asarray(lbs, float), np.asarray(ubs, float)
     batch = generate_batch(batch_size, lbs, ubs)
     if incumbent:
@@ -151,16 +162,17 @@ def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_it
     if device_solve:
         plan = _plan_for(sur, horizon, tp.rnstream_sequence.shape[0], batch.shape[1], es.get_starts().shape[1], lbs,
                          ubs, traj.θ[0], device, {})
-        r = _device_solve(plan, batch, tp, es, sgd_iterations, eta, solver, incumbent)
+        r = _device_solve(plan, batch, tp, es, sgd_iterations, eta, solver, incumbent, variance_reduction)
         if trace is not None:
             trace.append(dict(batch=batch, x=r["x"], means=r["means"][:, 0], pick=int(r["pick"][0]),
                               result=r["result"]))
         return r["xnext"][:, 0].copy(), float(r["mean"][0])
     opts = [StandardSGA(η=eta) if solver == "sga" else BoxAdam(lbs, ubs, η=eta) for _ in range(batch.shape[1])]
-    x, history = stochastic_solve_batch(opts, sur, tp, es, batch, T=traj, iterations=sgd_iterations, device=device)
+    x, history = stochastic_solve_batch(opts, sur, tp, es, batch, T=traj, iterations=sgd_iterations, device=device,
+                                        variance_reduction=variance_reduction)
     x = np.clip(x, lbs[:, None], ubs[:, None])
-    etos = simulate_trajectory_mc_batch(traj, tp, x, es.get_starts(), with_gradient=False, device=device).etos(
-        with_gradient=False)
+    etos = simulate_trajectory_mc_batch(traj, tp, x, es.get_starts(), with_gradient=False, device=device,
+                                        variance_reduction=variance_reduction).etos(with_gradient=False)
     k, means = pick_restart(sur, x, etos, lbs, ubs, incumbent)
     if trace is not None:
         trace.append(dict(batch=batch, x=x.copy(), means=means, pick=k, history=history))
@@ -183,14 +195,16 @@ def pick_restart(sur, x, etos, lbs, ubs, incumbent):
 
 
 def rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta, eta=0.01,
-                        device=0, solver="sga", incumbent=True, trace=None, device_solve=False):
+                        device=0, solver="sga", incumbent=True, trace=None, device_solve=False,
+                        variance_reduction=False):
     """rollout_solve for S surrogates of equal size at once (the lockstep trials of run(...,
     parallel_trials=k)): the same Sobol batch on each, its own incumbent restart, the outer ascent of
     all S·R restarts with one rollout launch per SGA iteration (stochastic_solve_multi) and one for
     the final ETO means.  Returns [(xnext, mean)] per surrogate, each what rollout_solve returns on
     that surrogate alone.  `trace`, a list, receives one dict per call (x0 d×R×S, the final points,
     the final ETO means R×S, the picks; the host loop adds its `history`).  device_solve=True: one
-    mrbo_rollout_solve call on the surrogate batch instead of the host-driven loop, same results."""
+    mrbo_rollout_solve call on the surrogate batch instead of the host-driven loop, same results.
+    variance_reduction=True: the control-variate ETO rows, as rollout_solve."""
     lbs, ubs = np.asarray(lbs, float), np.asarray(ubs, float)
     batch = generate_batch(batch_size, lbs, ubs)
     batches = [np.hstack([batch, incumbent_start(s, lbs, ubs)[:, None]]) if incumbent else batch for s in surs]
@@ -203,16 +217,18 @@ def rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts,
     if device_solve:
         plan = _plan_for_multi(list(surs), horizon, tp.rnstream_sequence.shape[0], x0.shape[1],
                                es.get_starts().shape[1], lbs, ubs, trajs[0].θ[0], device, {})
-        r = _device_solve(plan, x0, tp, es, sgd_iterations, eta, solver, incumbent)
+        r = _device_solve(plan, x0, tp, es, sgd_iterations, eta, solver, incumbent, variance_reduction)
         if trace is not None:
             trace.append(dict(batch=x0, x=r["x"], means=r["means"], pick=[int(k) for k in r["pick"]],
                               result=r["result"]))
         return [(r["xnext"][:, q].copy(), float(r["mean"][q])) for q in range(len(trajs))]
     opts = [[StandardSGA(η=eta) if solver == "sga" else BoxAdam(lbs, ubs, η=eta) for _ in range(x0.shape[1])]
             for _ in surs]
-    x, history = stochastic_solve_multi(opts, surs, tp, es, x0, Ts=trajs, iterations=sgd_iterations, device=device)
+    x, history = stochastic_solve_multi(opts, surs, tp, es, x0, Ts=trajs, iterations=sgd_iterations, device=device,
+                                        variance_reduction=variance_reduction)
     x = np.clip(x, lbs[:, None, None], ubs[:, None, None])
-    brs = simulate_trajectory_mc_multi(trajs, tp, x, es.get_starts(), with_gradient=False, device=device)
+    brs = simulate_trajectory_mc_multi(trajs, tp, x, es.get_starts(), with_gradient=False, device=device,
+                                       variance_reduction=variance_reduction)
     out, picks, all_means = [], [], []
     for q, s in enumerate(surs):
         xq = x[:, :, q]
@@ -239,7 +255,7 @@ def _check_parallel_trials(parallel_trials, reuse_surrogate):
 def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, mc_samples=200, batch_size=8,
         sgd_iterations=50, optimize=False, seed=1906, device=0, log=print, rules=("ei", "poi", "lcb"), eta=0.01,
         initial_observations=INITIAL_OBSERVATIONS, solver="sga", fmini_over_capacity=True, incumbent=True,
-        reuse_surrogate=True, parallel_trials=1, device_mle=False, device_solve=False):
+        reuse_surrogate=True, parallel_trials=1, device_mle=False, device_solve=False, variance_reduction=False):
     """The experiment loop; `rules` selects a subset of the reference's three acquisitions (all by
     default, as nonmyopic_bayesopt.jl), `eta` the StandardSGA step of the build-defined solver
     (default 0.01, StandardSGA's own default, optimizers.jl:9),
@@ -260,7 +276,9 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     (mle.optimize(..., device=True)); the default keeps the host-driven loop.
     device_solve=True: every acquisition solve is one device-resident call (mrbo_rollout_solve: the
     ascent, the final evaluation and the pick) with the host loop's results; the default keeps the
-    host-driven loop."""
+    host-driven loop.
+    variance_reduction=True (the reference's --variance-reduction, nonmyopic_bayesopt.jl:64-66): every
+    acquisition solve uses EI0 as a control variate (rollout_solve), on either solve path."""
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
@@ -301,7 +319,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 t0 = time.perf_counter()
                 picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
                                             theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
-                                            device_solve=device_solve)
+                                            device_solve=device_solve, variance_reduction=variance_reduction)
                 dt = time.perf_counter() - t0
                 for s, r, (xnext, _), initial_best in zip(surs, rec, picks, initial_bests):
                     r["times"][b] = dt
@@ -341,7 +359,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 t0 = time.perf_counter()
                 xnext, _ = rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
                                          theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
-                                         device_solve=device_solve)
+                                         device_solve=device_solve, variance_reduction=variance_reduction)
                 times[b] = time.perf_counter() - t0
                 observed_best = float(np.min(sur.get_active_observations()))
                 regrets[b] = simple_regret(true_minimum, observed_best)
@@ -533,6 +551,8 @@ def parse(argv=None):
                     help="with --optimize: run the MLE refit's minimisation as one device-resident call")
     ap.add_argument("--device-solve", action="store_true",
                     help="run every acquisition solve as one device-resident call (same results)")
+    ap.add_argument("--variance-reduction", action="store_true",
+                    help="Use EI as a control variate for variance reduction")
     return ap.parse_args(argv)
 
 
@@ -541,7 +561,7 @@ def main(argv=None):
     run(a.function_name, a.output_dir, budget=a.budget, trials=a.trials, starts=a.starts, horizon=a.horizon,
         mc_samples=a.mc_samples, batch_size=a.batch_size, sgd_iterations=a.sgd_iterations, optimize=a.optimize,
         seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1,
-        device_mle=a.device_mle, device_solve=a.device_solve)
+        device_mle=a.device_mle, device_solve=a.device_solve, variance_reduction=a.variance_reduction)
 
 
 if __name__ == "__main__":

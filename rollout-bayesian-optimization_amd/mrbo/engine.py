@@ -180,6 +180,53 @@ class RolloutPlan:
                                             p(out.get("grad_theta")), p(e), 0, ctypes.c_void_p(st.cuda_stream)))
         return e
 
+    # ---- the EI control variate (the specification is mrbo/variance.py) ----------
+    def alloc_control(self, with_gradient=True):
+        """Device outputs of simulate_control: values0, status0 and, with_gradient, grad_x0."""
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        T = self.M * self.R * self.S
+        out = dict(values0=torch.empty(T, dtype=torch.float64, device=dev),
+                   status0=torch.empty(T, dtype=torch.int32, device=dev))
+        if with_gradient:
+            out["grad_x0"] = torch.empty(self.d * T, dtype=torch.float64, device=dev)
+        return out
+
+    def simulate_control(self, x0s, rnstream, xstarts, ctl=None, with_gradient=True, stream=None):
+        """mrbo_simulate_control on device tensors: the plan's rollout launch run to horizon 0 -- the
+        control samples of the trajectories `simulate` runs from the same x0s and rnstream (the
+        plan's full stream: its step-0 slab is read).  ctl: the dict of alloc_control (allocated
+        when None; without "grad_x0" the launch takes MRBO_FLAG_NO_GRADIENT)."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if ctl is None:
+            ctl = self.alloc_control(with_gradient)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        flags = 0 if "grad_x0" in ctl else _lib.MRBO_FLAG_NO_GRADIENT
+        _lib.check(self.lib.mrbo_simulate_control(self.handle, p(x0s), p(rnstream), p(xstarts), p(ctl["values0"]),
+                                                  p(ctl.get("grad_x0")), p(ctl["status0"]), flags,
+                                                  ctypes.c_void_p(st.cuda_stream)))
+        return ctl
+
+    def eto_cv(self, x0s, out, ctl, want_beta=True, stream=None):
+        """mrbo_eto_reduce_cv: the ETO rows of `out` (simulate) with `ctl` (simulate_control at the
+        same x0s) as the control.  Returns (eto W·R·S, beta (1+d)·R·S or None), device tensors."""
+        torch = _torch()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        dev = f"cuda:{self.device}"
+        W = 2 + 2 * self.d + 2
+        e = torch.empty(W * self.R * self.S, dtype=torch.float64, device=dev)
+        b = torch.empty((1 + self.d) * self.R * self.S, dtype=torch.float64, device=dev) if want_beta else None
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self.lib.mrbo_eto_reduce_cv(self.handle, p(x0s), p(out["values"]), p(out.get("grad_x")),
+                                               p(out.get("grad_theta")), p(ctl["values0"]), p(ctl.get("grad_x0")),
+                                               p(e), p(b), 0, ctypes.c_void_p(st.cuda_stream)))
+        return e, b
+
+    def set_control_variate(self, on):
+        """mrbo_plan_set_control_variate: rollout_solve's rows become eto_cv's (default off)."""
+        _lib.check(self.lib.mrbo_plan_set_control_variate(self.handle, int(bool(on))))
+
     def partial_moments(self, out, M_local, stream=None):
         """mrbo_partial_moments: this shard's (W·R) [Σ, M2] rows, device tensor (parallel.py)."""
         torch = _torch()

@@ -121,8 +121,11 @@ class BatchResult:
 
 
 def simulate_trajectory_mc_batch(T, tp, x0s, inner_solve_xstarts, with_gradient=True, dual_y_dx=None, replay_x=None,
-                                 want_policy=False, want_obs=False, device=0, rnstream=None, **opts):
-    """R restarts (columns of x0s) × tp.mc_iters samples in one kernel launch."""
+                                 want_policy=False, want_obs=False, device=0, rnstream=None,
+                                 variance_reduction=False, **opts):
+    """R restarts (columns of x0s) × tp.mc_iters samples in one kernel launch.  variance_reduction=True:
+    a second launch at horizon 0 follows and the ETO rows are the control-variate ones
+    (RolloutPlan.simulate_control / eto_cv); the per-trajectory outputs are unchanged."""
     import torch
     x0s = np.asarray(x0s, dtype=np.float64)
     if x0s.ndim == 1:
@@ -140,8 +143,17 @@ def simulate_trajectory_mc_batch(T, tp, x0s, inner_solve_xstarts, with_gradient=
     drp = None if replay_x is None else to_device(replay_x, dev)
     out = plan.alloc_outputs(with_gradient=with_gradient, want_policy=want_policy, want_obs=want_obs)
     plan.simulate(dx0, drn, dxs, out, dual_y_dx=ddy, replay_x=drp)
-    eto = plan.eto(out)
+    eto = _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction)
     return BatchResult(plan, out, eto)
+
+
+def _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction):
+    """The ETO rows of a launch: mrbo_eto_reduce, or with variance_reduction the control launch at
+    the same x0 and mrbo_eto_reduce_cv."""
+    if not variance_reduction:
+        return plan.eto(out)
+    ctl = plan.simulate_control(dx0, drn, dxs, with_gradient=with_gradient)
+    return plan.eto_cv(dx0, out, ctl, want_beta=False)[0]
 
 
 class _PlanView:
@@ -164,7 +176,8 @@ def check_multi_x0s(x0s, S, d=None):
 
 
 def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient=True, dual_y_dx=None,
-                                 replay_x=None, want_policy=False, want_obs=False, device=0, rnstream=None, **opts):
+                                 replay_x=None, want_policy=False, want_obs=False, device=0, rnstream=None,
+                                 variance_reduction=False, **opts):
     """simulate_trajectory_mc_batch for S trajectories on S DIFFERENT base surrogates (Ts) in ONE
     kernel launch (RolloutPlan.from_surrogates): x0s is d×R×S -- R restarts per surrogate --, tp,
     the MC stream and the inner starts are shared, dual_y_dx / replay_x are d×h×M×R×S.  Returns one
@@ -192,10 +205,11 @@ def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient
     dev = f"cuda:{device}"
     drn = rn if isinstance(rn, torch.Tensor) else to_device(rn, dev)
     out = plan.alloc_outputs(with_gradient=with_gradient, want_policy=want_policy, want_obs=want_obs)
-    plan.simulate(to_device(x0s, dev), drn, to_device(inner_solve_xstarts, dev), out,
+    dx0, dxs = to_device(x0s, dev), to_device(inner_solve_xstarts, dev)
+    plan.simulate(dx0, drn, dxs, out,
                   dual_y_dx=None if dual_y_dx is None else to_device(dual_y_dx, dev),
                   replay_x=None if replay_x is None else to_device(replay_x, dev))
-    eto = plan.eto(out)
+    eto = _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction)   # variance_reduction: as the batch call
     view = _PlanView(plan)
     W = 2 + 2 * d + 2
     res = []

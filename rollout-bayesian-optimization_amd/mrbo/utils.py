@@ -144,13 +144,15 @@ def stochastic_solve(optimizer, surrogate, tp, es, start, T=None, iterations=50,
     return x[:, 0]
 
 
-def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iterations=50, device=0, **opts):
+def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iterations=50, device=0,
+                           variance_reduction=False, **opts):
     """stochastic_solve_batch for S surrogates at once: `starts` is d×R×S (R restarts on each
     surrogate), `optimizers` S lists of R optimizers.  The loop of stochastic_solve_batch over the
     S·R restarts with ONE batched rollout launch per iteration (simulate_trajectory_mc_multi); every
     restart keeps its own optimizer state and eswavs stop flag, so surrogate q's restarts move
     exactly as stochastic_solve_batch(optimizers[q], surrogates[q], tp, es, starts[:, :, q]) moves
-    them.  Returns (x d×R×S, history: per iteration, per surrogate, the R ETOs)."""
+    them.  variance_reduction=True: every iteration's ETO rows are the control-variate ones (DESIGN.md
+    §16).  Returns (x d×R×S, history: per iteration, per surrogate, the R ETOs)."""
     from .rollout import check_multi_x0s, simulate_trajectory_mc_multi
     from .surrogates import FantasySurrogate
     from .trajectory import Trajectory
@@ -170,7 +172,8 @@ def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iter
     for _ in range(iterations):
         if not active.any():
             break
-        brs = simulate_trajectory_mc_multi(Ts, tp, x, es.get_starts(), device=device, **opts)
+        brs = simulate_trajectory_mc_multi(Ts, tp, x, es.get_starts(), device=device,
+                                           variance_reduction=variance_reduction, **opts)
         etos = [br.etos() for br in brs]
         history.append(etos)
         for q in range(S):
@@ -185,9 +188,11 @@ def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iter
     return x, history
 
 
-def stochastic_solve_batch(optimizers, surrogate, tp, es, starts, T=None, iterations=50, device=0, **opts):
+def stochastic_solve_batch(optimizers, surrogate, tp, es, starts, T=None, iterations=50, device=0,
+                           variance_reduction=False, **opts):
     """R restarts of the outer ascent at once: one batched rollout launch per SGA iteration;
-    each restart keeps its own optimizer state and eswavs stop flag."""
+    each restart keeps its own optimizer state and eswavs stop flag.  variance_reduction=True: every
+    iteration's ETO rows are the control-variate ones (a second launch at horizon 0)."""
     from .rollout import simulate_trajectory_mc_batch
     from .surrogates import FantasySurrogate
     from .trajectory import Trajectory
@@ -201,7 +206,8 @@ def stochastic_solve_batch(optimizers, surrogate, tp, es, starts, T=None, iterat
     for _ in range(iterations):
         if not active.any():
             break
-        br = simulate_trajectory_mc_batch(T, tp, x, es.get_starts(), device=device, **opts)
+        br = simulate_trajectory_mc_batch(T, tp, x, es.get_starts(), device=device,
+                                          variance_reduction=variance_reduction, **opts)
         etos = br.etos()
         history.append(etos)
         for r in range(R):
