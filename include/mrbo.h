@@ -500,6 +500,31 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t S, int32_t nt, con
                            const double* lower, const double* upper, const mrbo_mle_opts_t* opts, double* theta,
                            double* nll, double* grad, int32_t* iters, int32_t* result, uint32_t flags, void* stream);
 
+/* The profiled-amplitude likelihood (build-defined, no reference counterpart): the data r = s->y are
+ * modelled as r = s·g with g ~ GP(0, ψ_θ) + σn2 noise, and the amplitude sits at its closed-form
+ * maximiser ŝ²(θ) = q/N, q = rᵀc, c = K⁻¹r, K = Ψ(θ) + σn2·I (the caller centres r).  What is left is
+ *   ll[p]        = −(N/2)·log(q/N) − Σ log L_ii − (N/2)(1 + log 2π)
+ *   grad[p·nt+t] = (N/(2q))·(cᵀ δK_t c) − tr(K⁻¹ δK_t)/2
+ *   s2[p]        = q/N
+ * from the sums the plain fit's kernels already hold (same kernels, same launch, another epilogue).
+ * mrbo_gp_fit_profile_multi is mrbo_gp_fit_multi in every other respect -- layouts, checks, kernel
+ * selection, workspace, synchronisation, L_out and c_out (bit-identical to the plain call's: they
+ * do not depend on the amplitude) -- with s2 (P×S, as ll; not NULL: MRBO_ERR_ARG) as one more
+ * output.  status[p] = 2 marks a slot whose q is not positive and finite (constant data: r = 0
+ * after centring): ll, grad and s2 are NaN there, and every other slot of the launch is as it
+ * would be without it, as for status 1. */
+int mrbo_gp_fit_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas,
+                              double* ll, double* grad, double* s2, int32_t* status, double* L_out, double* c_out,
+                              uint32_t flags, void* stream);
+/* mrbo_gp_optimize_multi minimising −ll_p: the fit launches run in profile mode, the step kernel
+ * and every rule of the minimisation are the same.  s2 (S; device pointer unless
+ * MRBO_FLAG_HOST_POINTERS; not NULL: MRBO_ERR_ARG) receives ŝ² at the returned theta, the accepted
+ * point's (NaN where the start's fit failed). */
+int mrbo_gp_optimize_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t nt, const double* theta0,
+                                   const double* lower, const double* upper, const mrbo_mle_opts_t* opts,
+                                   double* theta, double* nll, double* grad, double* s2, int32_t* iters,
+                                   int32_t* result, uint32_t flags, void* stream);
+
 /* Host helpers (HOST memory). */
 int mrbo_rnstream(int32_t M, int32_t d, int32_t H, double* out);                 /* M×(d+1)×H */
 int mrbo_initial_guesses(int32_t n, int32_t d, const double* lbs, const double* ubs, double* out); /* d×(n+2) */

@@ -16,6 +16,7 @@
 #include "../../include/mrbo.h"
 #define MRBO_API_TU
 #include "mrbo_dispatch.h"
+#include "mrbo_gpfit.h"
 #include "mrbo_mle.h"
 #include "mrbo_solve.h"
 #include "mrbo_cv.h"
@@ -1711,30 +1712,32 @@ static int gp_fit_stage(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const
 }
 
 // one launch of grid (P, S) on `st`, not synchronised
-static hipError_t gp_fit_launch(int P, int S, hipStream_t st, const GpFitParams& q) {
-  launch_gpfit(P, S, st, q);
+static hipError_t gp_fit_launch(int P, int S, hipStream_t st, const GpFitParams& q, const GpFitMode& pm) {
+  launch_gpfit(P, S, st, q, pm);
   return hipGetLastError();
 }
 
-// the outputs of a host call, after the stream has synchronised: [ll | grad | status] from the
-// pinned block `h`, the factors and coefficients straight from the device
+// the outputs of a host call, after the stream has synchronised: [ll | grad | s2 (profile mode) |
+// status] from the pinned block `h`, the factors and coefficients straight from the device
 static int gp_fit_copy_back(const GpFitParams& q, const void* h_, size_t PS, size_t N, double* ll, double* grad,
-                            int32_t* status, double* L_out, double* c_out) {
+                            double* s2, int32_t* status, double* L_out, double* c_out) {
   const double* h = (const double*)h_;
   const size_t NTP = (size_t)q.nt * PS;
   std::memcpy(ll, h, sizeof(double) * PS);
   std::memcpy(grad, h + PS, sizeof(double) * NTP);
-  std::memcpy(status, h + PS + NTP, sizeof(int32_t) * PS);
+  if (s2) std::memcpy(s2, h + PS + NTP, sizeof(double) * PS);
+  std::memcpy(status, h + PS + NTP + (s2 ? PS : 0), sizeof(int32_t) * PS);
   if (L_out) HIP_TRY(hipMemcpy(L_out, q.L_out, sizeof(double) * N * N * PS, hipMemcpyDeviceToHost));
   if (c_out) HIP_TRY(hipMemcpy(c_out, q.c_out, sizeof(double) * N * PS, hipMemcpyDeviceToHost));
   return MRBO_OK;
 }
 
-// mrbo_gp_fit_multi and, as its S = 1 case, mrbo_gp_fit_theta
+// mrbo_gp_fit_multi, as its S = 1 case mrbo_gp_fit_theta, and with `profile` mrbo_gp_fit_profile_multi
+// (s2: P×S, profile mode only)
 static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_t nt, const double* thetas, double* ll,
-                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream,
-                       bool multi) {
-  if (!s || !thetas || !ll || !grad || !status || np < 1) return fail(MRBO_ERR_ARG, "null argument");
+                       double* grad, double* s2, int32_t* status, double* L_out, double* c_out, uint32_t flags,
+                       void* stream, bool multi, bool profile) {
+  if (!s || !thetas || !ll || !grad || !status || np < 1 || (profile && !s2)) return fail(MRBO_ERR_ARG, "null argument");
   if (const int rc = gp_fit_check(s, ns, nt, multi)) return rc;
   const int d = s->d, N = s->N;
   hipStream_t st = (hipStream_t)stream;
@@ -1744,7 +1747,8 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
   // device block and one copy back
   GpFitStaged f(host ? NTP : 0, DN * S + N * S + S);
   GpFitParams& q = f.q;
-  const size_t out_bytes = sizeof(double) * (PS + NTP) + sizeof(int32_t) * PS;
+  const size_t out_bytes = sizeof(double) * (PS + NTP + (profile ? PS : 0)) + sizeof(int32_t) * PS;
+  GpFitMode pm{profile ? 1 : 0, profile ? s2 : nullptr};
   q.thetas = thetas;
   q.ll = ll;
   q.grad = grad;
@@ -1757,7 +1761,8 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
       return fail(MRBO_ERR_NOMEM, "staging allocation failed");
     q.ll = (double*)dout;
     q.grad = q.ll + PS;
-    q.status = (int*)(q.grad + NTP);
+    if (profile) pm.s2 = q.grad + NTP;
+    q.status = (int*)(q.grad + NTP + (profile ? PS : 0));
   }
   Pinned pin_out(host ? out_bytes : 0);
   if (host && !pin_out.p) return fail(MRBO_ERR_NOMEM, "pinned staging");
@@ -1792,7 +1797,7 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
   // memory a running kernel still uses to another call), and keeps them out of the pool when
   // even that fails
   {
-    hipError_t e = gp_fit_launch(np, ns, st, q);
+    hipError_t e = gp_fit_launch(np, ns, st, q, pm);
     if (e == hipSuccess) e = hipEventRecord(gev[1], st);
     // the small outputs of a host call come back on the same stream (into pinned memory), so
     // one synchronisation covers the kernel and the copy
@@ -1810,18 +1815,24 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
     float ms = -1.f;
     if (hipEventElapsedTime(&ms, gev[0], gev[1]) == hipSuccess) g_gpfit_ms = ms;
   }
-  if (host) return gp_fit_copy_back(q, pin_out.p, PS, (size_t)N, ll, grad, status, L_out, c_out);
+  if (host) return gp_fit_copy_back(q, pin_out.p, PS, (size_t)N, ll, grad, profile ? s2 : nullptr, status, L_out, c_out);
   return MRBO_OK;
 }
 
 int mrbo_gp_fit_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas, double* ll,
                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
-  return gp_fit_impl(s, S, P, nt, thetas, ll, grad, status, L_out, c_out, flags, stream, true);
+  return gp_fit_impl(s, S, P, nt, thetas, ll, grad, nullptr, status, L_out, c_out, flags, stream, true, false);
+}
+
+int mrbo_gp_fit_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, int32_t nt, const double* thetas,
+                              double* ll, double* grad, double* s2, int32_t* status, double* L_out, double* c_out,
+                              uint32_t flags, void* stream) {
+  return gp_fit_impl(s, S, P, nt, thetas, ll, grad, s2, status, L_out, c_out, flags, stream, true, true);
 }
 
 int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const double* thetas, double* ll,
                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
-  return gp_fit_impl(s, 1, np, nt, thetas, ll, grad, status, L_out, c_out, flags, stream, false);
+  return gp_fit_impl(s, 1, np, nt, thetas, ll, grad, nullptr, status, L_out, c_out, flags, stream, false, false);
 }
 
 int mrbo_gp_fit(const mrbo_surrogate_t* s, int32_t np, const double* ells, double* ll, double* dll, int32_t* status,
@@ -1870,11 +1881,13 @@ struct CheckEvents {
 };
 }  // namespace
 
-int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const double* theta0,
-                           const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
-                           double* nll, double* grad, int32_t* iters, int32_t* result, uint32_t flags, void* stream) {
+// mrbo_gp_optimize_multi and, with `profile`, mrbo_gp_optimize_profile_multi (s2: S, profile mode only)
+static int gp_optimize_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const double* theta0,
+                            const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
+                            double* nll, double* grad, double* s2, int32_t* iters, int32_t* result, uint32_t flags,
+                            void* stream, bool profile) {
   // every argument check comes before the first HIP call
-  if (!s || !theta0 || !lower || !upper || !theta || !nll || !grad || !iters || !result)
+  if (!s || !theta0 || !lower || !upper || !theta || !nll || !grad || !iters || !result || (profile && !s2))
     return fail(MRBO_ERR_ARG, "gp_optimize_multi: null argument");
   if (const int rc = gp_fit_check(s, ns, nt, true)) return rc;
   MleParams mp{};
@@ -1908,10 +1921,12 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, co
   const size_t S = (size_t)ns, NT = (size_t)nt * S, P = MLE_STEPS, M = (size_t)mp.m;
   // the starts of a host call travel with the data sets
   GpFitStaged f(host ? NT : 0, (size_t)d * N * S + (size_t)N * S + S);
-  // the minimiser's device block: doubles [trial | ll | ∇ll | s | y | α], then ints [status | ring | check];
-  // a host call's outputs [theta | nll | grad | iters] in a block of their own, one copy back
-  const size_t n_dbl = NT * P + P * S + NT * P + 2 * NT * M + M * S, n_int = P * S + 3 * S + MLE_NCHK;
-  const size_t out_bytes = sizeof(double) * (2 * NT + S) + sizeof(int32_t) * S;
+  // the minimiser's device block: doubles [trial | ll | ∇ll | s | y | α | ŝ² (profile mode)], then ints
+  // [status | ring | check]; a host call's outputs [theta | nll | grad | s2 (profile mode) | iters] in a
+  // block of their own, one copy back
+  const size_t S2 = profile ? S : 0;
+  const size_t n_dbl = NT * P + P * S + NT * P + 2 * NT * M + M * S + P * S2, n_int = P * S + 3 * S + MLE_NCHK;
+  const size_t out_bytes = sizeof(double) * (2 * NT + S + S2) + sizeof(int32_t) * S;
   double* dw = (double*)f.sg.slot(sizeof(double) * n_dbl + sizeof(int32_t) * n_int);
   char* dout = host ? (char*)f.sg.slot(out_bytes) : nullptr;
   if (!dw || (host && !dout)) return fail(MRBO_ERR_NOMEM, "gp_optimize_multi: device buffers");
@@ -1929,7 +1944,8 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, co
   mp.hs = dgll + NT * P;
   mp.hy = mp.hs + NT * M;
   mp.al = mp.hy + NT * M;
-  int* dst = (int*)(mp.al + M * S);
+  GpFitMode pm{profile ? 1 : 0, profile ? mp.al + M * S : nullptr};
+  int* dst = (int*)(mp.al + M * S + P * S2);
   mp.ring = dst + P * S;
   mp.check = mp.ring + 3 * S;
   mp.ll = dll_;
@@ -1938,7 +1954,9 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, co
   mp.x = host ? (double*)dout : theta;
   mp.f = host ? mp.x + NT : nll;
   mp.g = host ? mp.f + S : grad;
-  mp.it = host ? (int*)(mp.g + NT) : (int*)iters;
+  mp.s2_fit = pm.s2;
+  mp.s2 = !profile ? nullptr : host ? mp.g + NT : s2;
+  mp.it = host ? (int*)(mp.g + NT + S2) : (int*)iters;
   f.q.ll = dll_;
   f.q.grad = dgll;
   f.q.status = dst;
@@ -1977,7 +1995,7 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, co
     ++j;
     const int k = (j - 1) % MLE_NCHK;
     f.q.thetas = j == 1 ? mp.x : mp.trial;
-    hipError_t e = gp_fit_launch(j == 1 ? 1 : (int)P, ns, st, f.q);
+    hipError_t e = gp_fit_launch(j == 1 ? 1 : (int)P, ns, st, f.q, pm);
     if (e != hipSuccess) return bail("fit launch", e);
     launch_mle_step(j == 1, k, st, mp);
     e = hipGetLastError();
@@ -2004,11 +2022,26 @@ int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, co
     std::memcpy(theta, h, sizeof(double) * NT);
     std::memcpy(nll, h + NT, sizeof(double) * S);
     std::memcpy(grad, h + NT + S, sizeof(double) * NT);
-    std::memcpy(iters, h + 2 * NT + S, sizeof(int32_t) * S);
+    if (profile) std::memcpy(s2, h + 2 * NT + S, sizeof(double) * S);
+    std::memcpy(iters, h + 2 * NT + S + S2, sizeof(int32_t) * S);
   }
   result[0] = j;                             // rounds launched
   result[1] = stopped_at ? stopped_at : j;   // the round after which no problem ran
   return MRBO_OK;
+}
+
+int mrbo_gp_optimize_multi(const mrbo_surrogate_t* s, int32_t S, int32_t nt, const double* theta0,
+                           const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
+                           double* nll, double* grad, int32_t* iters, int32_t* result, uint32_t flags, void* stream) {
+  return gp_optimize_impl(s, S, nt, theta0, lower, upper, o, theta, nll, grad, nullptr, iters, result, flags, stream,
+                          false);
+}
+
+int mrbo_gp_optimize_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t nt, const double* theta0,
+                                   const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
+                                   double* nll, double* grad, double* s2, int32_t* iters, int32_t* result,
+                                   uint32_t flags, void* stream) {
+  return gp_optimize_impl(s, S, nt, theta0, lower, upper, o, theta, nll, grad, s2, iters, result, flags, stream, true);
 }
 
 int mrbo_plan_set_order(mrbo_plan_t* P, const int32_t* order, int64_t n) {

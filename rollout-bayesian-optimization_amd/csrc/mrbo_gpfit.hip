@@ -28,12 +28,17 @@
 // candidates each in ONE launch of grid (P, S): see gpfit_candidate below.  The arithmetic of a fit is
 // untouched, so block s of the outputs carries the bits of a launch on data set s alone;
 // mrbo_gp_fit_theta is the S = 1 launch.
+//
+// mrbo_gp_fit_profile_multi (no reference counterpart): the profiled-amplitude likelihood (GpFitMode,
+// mrbo_gpfit.h).  Each kernel body below is a template over PROFILE and compiled twice: the plain
+// kernel with the reference's epilogue, and the profile kernel, which forms ll_p, ∂ll_p and ŝ² from
+// the same sums (gpfit_profile_out) and takes the s2 output as one more argument.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 #include <utility>
 
-#include "mrbo_dispatch.h"
+#include "mrbo_gpfit.h"
 #include "gpfit_asm.h"
 
 namespace mrbo {
@@ -290,6 +295,31 @@ __device__ __forceinline__ void gr_kinv_block(const double (&v)[64], double (&kb
   (step(v[M]), ...);
 }
 
+// The epilogue of a profile-mode fit (PROFILE kernels; GpFitMode, mrbo_gpfit.h): the amplitude s² of y = s·g,
+// g ~ GP(0, ψ_θ) + σn2, has the closed-form maximiser ŝ² = q/N with q = yᵀc, and what is left is
+//   ll_p = −(N/2)·log(q/N) − Σ log L_ii − (N/2)(1 + log 2π),
+//   ∂ll_p/∂θ_t = (N/q)·(cᵀδK_t c)/2 − tr(K⁻¹δK_t)/2
+// from the sums the plain epilogue holds (yc = q, ld = Σ log L_ii, trs = tr/2, cgs = cᵀδK c/2).
+// Constant data (q ≤ 0 or not finite) has no amplitude: status 2 and NaN outputs.
+template <int NT>
+__device__ __forceinline__ void gpfit_profile_out(const GpFitParams& q, double* s2_out, int p, double yc,
+                                                  double ld, const double (&trs)[NT], const double (&cgs)[NT]) {
+  const double N = q.N;
+  if (!(yc > 0.0) || !(yc <= 1.79769313486231570815e308)) {
+    q.ll[p] = NAN;
+    for (int t = 0; t < NT; ++t) q.grad[(size_t)p * NT + t] = NAN;
+    s2_out[p] = NAN;
+    q.status[p] = 2;
+    return;
+  }
+  const double s2 = yc / N;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) q.grad[(size_t)p * NT + t] = cgs[t] / s2 - trs[t];
+  q.ll[p] = -0.5 * N * log(s2) - ld - 0.5 * N * (1.0 + log(2.0 * 3.141592653589793));
+  s2_out[p] = s2;
+  q.status[p] = 0;
+}
+
 // -DMRBO_GPFIT_STAMPS: cycles per phase of candidate 0 (one printf at the end): X staging, K rows,
 // Cholesky, c, L⁻¹, K⁻¹·δK traces
 #ifdef MRBO_GPFIT_STAMPS
@@ -302,8 +332,8 @@ __device__ __forceinline__ void gr_kinv_block(const double (&v)[64], double (&kb
 // alone runs the register phases (no workgroup barrier after the pairs)
 constexpr int GR_WAVES = 4;
 
-template <int NT>
-__global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q, int P) {
+template <int NT, bool PROFILE>
+__device__ __forceinline__ void gpfit_reg_body(const GpFitParams& q, int P, double* s2_out) {
   extern __shared__ __attribute__((aligned(16))) double gsm[];
   const int lane = threadIdx.x & 63, tid = threadIdx.x;
   if ((int)blockIdx.x >= P) return;   // whole workgroups
@@ -431,6 +461,7 @@ __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q,
     if (tid == 0) {
       q.ll[p] = NAN;
       for (int t = 0; t < NT; ++t) q.grad[(size_t)p * NT + t] = NAN;
+      if (PROFILE) s2_out[p] = NAN;
       q.status[p] = 1;
     }
     return;
@@ -472,7 +503,15 @@ __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q,
   }
   GR_STAMP(5);
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0 && PROFILE) {
+    double trs[NT], cgs[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {   // the full sums: halved
+      trs[t] = 0.5 * ((part[0][t] + part[1][t]) + (part[2][t] + part[3][t]));
+      cgs[t] = 0.5 * ((part[0][NT + t] + part[1][NT + t]) + (part[2][NT + t] + part[3][NT + t]));
+    }
+    gpfit_profile_out<NT>(q, s2_out, p, part[0][2 * NT], part[0][2 * NT + 1], trs, cgs);
+  } else if (tid == 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const double trs = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
@@ -501,8 +540,8 @@ __global__ void __launch_bounds__(64 * GR_WAVES) gpfit_reg_kernel(GpFitParams q,
 // N³/3 + N³/6 + N³/6 FMAs instead of the workspace kernel's N³/3 + N³/2·nt + N³/6.
 constexpr int GL_N = 128, GL_LD = 129, GL_THREADS = 256;
 
-template <int NT>
-__global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, int P) {
+template <int NT, bool PROFILE>
+__device__ __forceinline__ void gpfit_lds_body(const GpFitParams& q, int P, double* s2_out) {
   extern __shared__ __attribute__((aligned(16))) double gsm[];
   double* S = gsm;                      // GL_N × GL_LD
   double* XS = S + GL_N * GL_LD;        // X[u][i] at u·GL_N + i (u < d ≤ 16)
@@ -591,6 +630,7 @@ __global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, in
     if (tid == 0) {
       q.ll[p] = NAN;
       for (int t = 0; t < NT; ++t) q.grad[(size_t)p * NT + t] = NAN;
+      if (PROFILE) s2_out[p] = NAN;
       q.status[p] = 1;
     }
     return;
@@ -704,7 +744,15 @@ __global__ void __launch_bounds__(GL_THREADS) gpfit_lds_kernel(GpFitParams q, in
     if (lane == 0) { part[w][t] = trs; part[w][NT + t] = cgs; }
   }
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0 && PROFILE) {
+    double trs[NT], cgs[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {   // Σ_{j<i}: half of the full sums already
+      trs[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+      cgs[t] = (part[0][NT + t] + part[1][NT + t]) + (part[2][NT + t] + part[3][NT + t]);
+    }
+    gpfit_profile_out<NT>(q, s2_out, p, part[0][2 * NT], part[0][2 * NT + 1], trs, cgs);
+  } else if (tid == 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {   // both triangles: 2·Σ_{j<i}
       const double trs = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
@@ -887,8 +935,8 @@ __device__ __forceinline__ void tt_panel(double (&v)[TT], const double* Dk, cons
 #define TT_STAMP(k) ((void)0)
 #endif
 
-template <int NT>
-__global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, int P) {
+template <int NT, bool PROFILE>
+__device__ __forceinline__ void gpfit_tile_body(const GpFitParams& q, int P, double* s2_out) {
   extern __shared__ __attribute__((aligned(16))) double tsm[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if ((int)blockIdx.x >= P) return;   // whole workgroups
@@ -1141,6 +1189,7 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
     if (tid == 0) {
       q.ll[p] = NAN;
       for (int t = 0; t < NT; ++t) q.grad[(size_t)p * NT + t] = NAN;
+      if (PROFILE) s2_out[p] = NAN;
       q.status[p] = 1;
     }
     return;
@@ -1261,7 +1310,15 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
   }
   __syncthreads();
   TT_STAMP(7);
-  if (tid == 0) {
+  if (tid == 0 && PROFILE) {
+    double trs[NT], cgs[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {   // Σ_{j<i}: half of the full sums already
+      trs[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+      cgs[t] = (part[0][NT + t] + part[1][NT + t]) + (part[2][NT + t] + part[3][NT + t]);
+    }
+    gpfit_profile_out<NT>(q, s2_out, p, part[0][2 * NT], part[0][2 * NT + 1], trs, cgs);
+  } else if (tid == 0) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {   // both triangles: 2·Σ_{j<i}, halved by δlog_likelihood's 1/2
       const double trs = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
@@ -1287,6 +1344,22 @@ __global__ void __launch_bounds__(TT_THREADS) gpfit_tile_kernel(GpFitParams q, i
   if (q.c_out)
     for (int i = tid; i < N; i += TT_THREADS) q.c_out[(size_t)N * p + i] = yv[i];
 }
+
+// The kernels: each body above once with the plain epilogue -- signature and code of the kernels
+// before the profile mode existed -- and once with the profile epilogue and its s2 output.
+#define MRBO_GPFIT_KERNELS(name, bounds)                                                              \
+  template <int NT>                                                                                   \
+  __global__ void __launch_bounds__(bounds) gpfit_##name##_kernel(GpFitParams q, int P) {             \
+    gpfit_##name##_body<NT, false>(q, P, nullptr);                                                    \
+  }                                                                                                   \
+  template <int NT>                                                                                   \
+  __global__ void __launch_bounds__(bounds) gpfit_##name##_profile_kernel(GpFitParams q, int P, double* s2) { \
+    gpfit_##name##_body<NT, true>(q, P, s2);                                                          \
+  }
+MRBO_GPFIT_KERNELS(reg, 64 * GR_WAVES)
+MRBO_GPFIT_KERNELS(lds, GL_THREADS)
+MRBO_GPFIT_KERNELS(tile, TT_THREADS)
+#undef MRBO_GPFIT_KERNELS
 
 size_t gpfit_tile_lds(int d, int N) {
   const int NP = ((N + TT - 1) / TT) * TT;
@@ -1323,25 +1396,29 @@ size_t gpfit_launch_lds(const GpFitParams& q) {
   return dyn;
 }
 
-void launch_gpfit(int P, int S, hipStream_t st, const GpFitParams& q) {
+// one launch of kernel K (plain) or KP (profile: s2 as one more argument)
+#define MRBO_GPFIT_LAUNCH(K, KP, block, lds)                                                  \
+  do {                                                                                        \
+    if (pm.profile) hipLaunchKernelGGL(KP, dim3(P, S), dim3(block), lds, st, q, P, pm.s2);    \
+    else hipLaunchKernelGGL(K, dim3(P, S), dim3(block), lds, st, q, P);                       \
+  } while (0)
+
+void launch_gpfit(int P, int S, hipStream_t st, const GpFitParams& q, const GpFitMode& pm) {
   if (gpfit_in_regs(q)) {
-    if (q.nt == 2)
-      hipLaunchKernelGGL(gpfit_reg_kernel<2>, dim3(P, S), dim3(64 * GR_WAVES), gpfit_reg_lds(2), st, q, P);
-    else
-      hipLaunchKernelGGL(gpfit_reg_kernel<1>, dim3(P, S), dim3(64 * GR_WAVES), gpfit_reg_lds(1), st, q, P);
+    if (q.nt == 2) MRBO_GPFIT_LAUNCH(gpfit_reg_kernel<2>, gpfit_reg_profile_kernel<2>, 64 * GR_WAVES, gpfit_reg_lds(2));
+    else MRBO_GPFIT_LAUNCH(gpfit_reg_kernel<1>, gpfit_reg_profile_kernel<1>, 64 * GR_WAVES, gpfit_reg_lds(1));
     return;
   }
   if (gpfit_in_lds(q)) {
-    if (q.nt == 2)
-      hipLaunchKernelGGL(gpfit_lds_kernel<2>, dim3(P, S), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
-    else
-      hipLaunchKernelGGL(gpfit_lds_kernel<1>, dim3(P, S), dim3(GL_THREADS), gpfit_lds_bytes(), st, q, P);
+    if (q.nt == 2) MRBO_GPFIT_LAUNCH(gpfit_lds_kernel<2>, gpfit_lds_profile_kernel<2>, GL_THREADS, gpfit_lds_bytes());
+    else MRBO_GPFIT_LAUNCH(gpfit_lds_kernel<1>, gpfit_lds_profile_kernel<1>, GL_THREADS, gpfit_lds_bytes());
     return;
   }
-  if (q.nt == 2)
-    hipLaunchKernelGGL(gpfit_tile_kernel<2>, dim3(P, S), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
-  else
-    hipLaunchKernelGGL(gpfit_tile_kernel<1>, dim3(P, S), dim3(TT_THREADS), gpfit_tile_lds(q.d, q.N), st, q, P);
+  if (q.nt == 2) MRBO_GPFIT_LAUNCH(gpfit_tile_kernel<2>, gpfit_tile_profile_kernel<2>, TT_THREADS, gpfit_tile_lds(q.d, q.N));
+  else MRBO_GPFIT_LAUNCH(gpfit_tile_kernel<1>, gpfit_tile_profile_kernel<1>, TT_THREADS, gpfit_tile_lds(q.d, q.N));
 }
+#undef MRBO_GPFIT_LAUNCH
+
+void launch_gpfit(int P, int S, hipStream_t st, const GpFitParams& q) { launch_gpfit(P, S, st, q, GpFitMode{0, nullptr}); }
 
 }  // namespace mrbo

@@ -30,6 +30,10 @@ struct MleParams {
   double* al;                      // m×S: the two-loop recursion's α
   int* ring;                       // 3×S: pairs held, position of the oldest, 1 while the problem runs
   int* check;                      // the check ring, one int per slot: problems still running
+  // profile-mode fits (mrbo_gp_optimize_profile_multi): the fit launches also write the profiled
+  // amplitude of every slot, and the iterate's is kept beside f.  Both null otherwise.
+  const double* s2_fit;            // P×S, as ll
+  double* s2;                      // S: ŝ² at the iterate
 };
 
 // x = clip(theta0) and every trial point = x; no pairs, no line search made, every problem running

@@ -81,6 +81,7 @@ __host__ __device__ int step_problem(const MleParams& p, int q, bool first) {
     for (int i = 0; i < NT; ++i) g[i] = -g[i];
     p.f[q] = f;
     store<NT>(p.g, q, g);
+    if (p.s2) p.s2[q] = p.s2_fit[q];
   } else {       // the line search: the first trial step that is finite and meets Armijo
     f = p.f[q];
     load<NT>(p.g, q, g);
@@ -135,6 +136,7 @@ __host__ __device__ int step_problem(const MleParams& p, int q, bool first) {
     store<NT>(p.x, q, x);
     p.f[q] = f;
     store<NT>(p.g, q, g);
+    if (p.s2) p.s2[q] = p.s2_fit[k0 + k];
     if (moved == 0.0) {
       *running = 0;
       return 0;

@@ -255,7 +255,8 @@ def _check_parallel_trials(parallel_trials, reuse_surrogate):
 def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, mc_samples=200, batch_size=8,
         sgd_iterations=50, optimize=False, seed=1906, device=0, log=print, rules=("ei", "poi", "lcb"), eta=0.01,
         initial_observations=INITIAL_OBSERVATIONS, solver="sga", fmini_over_capacity=True, incumbent=True,
-        reuse_surrogate=True, parallel_trials=1, device_mle=False, device_solve=False, variance_reduction=False):
+        reuse_surrogate=True, parallel_trials=1, device_mle=False, device_solve=False, variance_reduction=False,
+        standardize=False):
     """The experiment loop; `rules` selects a subset of the reference's three acquisitions (all by
     default, as nonmyopic_bayesopt.jl), `eta` the StandardSGA step of the build-defined solver
     (default 0.01, StandardSGA's own default, optimizers.jl:9),
@@ -278,7 +279,11 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     ascent, the final evaluation and the pick) with the host loop's results; the default keeps the
     host-driven loop.
     variance_reduction=True (the reference's --variance-reduction, nonmyopic_bayesopt.jl:64-66): every
-    acquisition solve uses EI0 as a control variate (rollout_solve), on either solve path."""
+    acquisition solve uses EI0 as a control variate (rollout_solve), on either solve path.
+    standardize=True (build-defined): the surrogates fit their output scale
+    (Surrogate(standardize=True): y = m + s·g), the acquisition runs on the standardised
+    observations and `optimize` maximises the profiled-amplitude likelihood.  Gaps, regrets, minimum
+    observations and the returned y stay in the objective's raw units."""
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
@@ -300,7 +305,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     sur = None
     if reuse_surrogate:    # :233 "Preallocate entire surrogate object and reuse"
         sur = Surrogate(Matern52(), np.zeros((testfn.dim, 1)), np.zeros(1), capacity=budget + initial_observations,
-                        σn2=1e-6)
+                        σn2=1e-6, standardize=standardize)
     for acq, rule, theta in zip(acquisitions, rules, dr_hypers):
         if reuse_surrogate:
             sur.set_decision_rule(rule)                                   # :241
@@ -308,7 +313,8 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
         for t0_ in range(0, trials if parallel_trials > 1 else 0, parallel_trials):
             chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
             surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
-                              capacity=budget + initial_observations, decision_rule=rule, σn2=1e-6) for t in chunk]
+                              capacity=budget + initial_observations, decision_rule=rule, σn2=1e-6,
+                              standardize=standardize) for t in chunk]
             for s in surs:
                 s.fmini_over_capacity = fmini_over_capacity
             ell_starts = [float(s.ψ.lengthscale) for s in surs]
@@ -349,7 +355,7 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 sur.reset(Xinit, yinit)                                   # :253
             else:
                 sur = Surrogate(Matern52(), Xinit, yinit, capacity=budget + initial_observations, decision_rule=rule,
-                                σn2=1e-6)
+                                σn2=1e-6, standardize=standardize)
             sur.fmini_over_capacity = fmini_over_capacity
             ell_start = float(sur.ψ.lengthscale)
             initial_best = float(np.min(yinit))
@@ -385,7 +391,7 @@ MYOPIC_RULES = {"ei": (EI, 0.0), "poi": (POI, 0.0), "lcb": (LCB, 2.0)}   # :151-
 def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed=1906, device=0, log=print,
                rules=("ei", "poi", "lcb"), optimize=True, initial_observations=INITIAL_OBSERVATIONS,
                reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False, parallel_trials=1,
-               device_mle=False):
+               device_mle=False, standardize=False):
     """myopic_bayesopt.jl's loop: per budget step xnext = multistart_base_solve!(sur, …; guesses =
     generate_initial_guesses(starts, lbs, ubs), θfixed) -- the deterministic multistart local solve of
     the analytic acquisition on the base surrogate (:224-233), here mrbo_base_solve on the device --
@@ -409,7 +415,8 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     parallel_trials=k > 1 (needs reuse_surrogate=False, else ValueError): up to k trials advance in
     lockstep, every budget step one mrbo_base_solve launch on their k surrogates (base_solve_multi).
     device_mle=True: optimize!'s minimisation runs as one device-resident call
-    (mle.optimize(..., device=True)); the default keeps the host-driven loop."""
+    (mle.optimize(..., device=True)); the default keeps the host-driven loop.
+    standardize=True: surrogates that fit their output scale, as in run."""
     from .rbf_optim import base_solve_batch, base_solve_multi, findmin_candidates, multistart_base_solve
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     from .utils import generate_initial_guesses
@@ -432,7 +439,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
         # capacity = BUDGET as the reference; it must hold the initial design (a reset! past
         # capacity is a BoundsError in Julia), so a budget below it gets the design's size
         sur = Surrogate(Matern52(), np.zeros((testfn.dim, 1)), np.zeros(1),
-                        capacity=capacity or max(budget, initial_observations), σn2=1e-6)
+                        capacity=capacity or max(budget, initial_observations), σn2=1e-6, standardize=standardize)
     for acq in rules:
         make_rule, theta = MYOPIC_RULES[acq]
         if reuse_surrogate:
@@ -442,7 +449,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
             surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
                               capacity=capacity or budget + initial_observations, decision_rule=make_rule(),
-                              σn2=1e-6) for t in chunk]
+                              σn2=1e-6, standardize=standardize) for t in chunk]
             ell_starts = [float(s.ψ.lengthscale) for s in surs]
             initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
             rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
@@ -489,7 +496,7 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                 sur.reset(Xinit, yinit)                                   # :217
             else:
                 sur = Surrogate(Matern52(), Xinit, yinit, capacity=capacity or budget + initial_observations,
-                                decision_rule=make_rule(), σn2=1e-6)
+                                decision_rule=make_rule(), σn2=1e-6, standardize=standardize)
             ell_start = float(sur.ψ.lengthscale)
             initial_best = float(np.min(yinit))
             times, gaps, allocs, regrets, minobs = (np.zeros(budget) for _ in range(5))
@@ -553,6 +560,9 @@ def parse(argv=None):
                     help="run every acquisition solve as one device-resident call (same results)")
     ap.add_argument("--variance-reduction", action="store_true",
                     help="Use EI as a control variate for variance reduction")
+    ap.add_argument("--standardize", action="store_true",
+                    help="fit the surrogate's output scale (mean and amplitude) and run the acquisition on the "
+                         "standardised observations; with --optimize the profiled-amplitude likelihood")
     return ap.parse_args(argv)
 
 
@@ -561,7 +571,8 @@ def main(argv=None):
     run(a.function_name, a.output_dir, budget=a.budget, trials=a.trials, starts=a.starts, horizon=a.horizon,
         mc_samples=a.mc_samples, batch_size=a.batch_size, sgd_iterations=a.sgd_iterations, optimize=a.optimize,
         seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1,
-        device_mle=a.device_mle, device_solve=a.device_solve, variance_reduction=a.variance_reduction)
+        device_mle=a.device_mle, device_solve=a.device_solve, variance_reduction=a.variance_reduction,
+        standardize=a.standardize)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,9 @@ launch for S surrogates × P candidates (mrbo_gp_fit_multi), projected_lbfgs_mul
 minimisations in lockstep through the same per-problem code, optimize_multi is optimize for a list.
 gp_optimize_multi runs those S minimisations as one device-resident call (mrbo_gp_optimize_multi:
 no host round trip per line search); lbfgs_scalar is the specification its step kernel is held to.
+The profiled-amplitude likelihood (build-defined, opt-in: profile=True / profile_amplitude=True)
+models the data as s·g, g ~ GP(0, ψ_θ) + σn2, with s² at its closed-form maximiser; the same
+kernels evaluate it (mrbo_gp_fit_profile_multi), profile_log_likelihood_host is its specification.
 """
 import ctypes
 import math
@@ -32,11 +35,69 @@ def _nt(s):
     return len(s.ψ.θ)
 
 
-def gp_fit_batch(s, thetas, want_fit=False):
+def _dpsi_dtheta(ψ, ρ):
+    """∂ψ/∂θ_t(ρ) in closed form (eval_Dθ_KXX's entries, radial_basis_functions.jl:264-284 by
+    ForwardDiff there): (nt, ...) -- ∂/∂ℓ, and ∂/∂p for Periodic."""
+    from .kernels import MATERN12, MATERN32, MATERN52, PERIODIC
+    l = ψ.lengthscale
+    if ψ.kind == PERIODIC:
+        p = ψ.period
+        u = np.pi * ρ / p
+        su = np.sin(u)
+        v = ψ(ρ)
+        return np.stack([v * 4.0 * su * su / l ** 3, v * 2.0 * u * np.sin(2.0 * u) / (l * l * p)])
+    if ψ.kind == MATERN52:
+        s = np.sqrt(5.0) * ρ / l
+        return (s * s / 3.0 * (1.0 + s) * np.exp(-s) / l)[None]
+    if ψ.kind == MATERN32:
+        s = np.sqrt(3.0) * ρ / l
+        return (s * s * np.exp(-s) / l)[None]
+    if ψ.kind == MATERN12:
+        s = ρ / l
+        return (s * np.exp(-s) / l)[None]
+    return (ψ(ρ) * ρ * ρ / l ** 3)[None]
+
+
+def profile_log_likelihood_host(X, y, ψ, σn2):
+    """The profiled-amplitude likelihood in float64 numpy, the specification of the device's profile
+    mode: the data r = y (d×N X, the caller centres y) are r = s·g with g ~ GP(0, ψ) + σn2 noise and
+    the amplitude at its closed-form maximiser ŝ² = q/N, q = rᵀK⁻¹r, K = Ψ + σn2·I:
+        ll_p       = −(N/2)·log(q/N) − Σ log L_ii − (N/2)(1 + log 2π)
+        ∂ll_p/∂θ_t = (N/(2q))·(cᵀ δK_t c) − tr(K⁻¹ δK_t)/2,   c = K⁻¹r.
+    Returns dict(ll, grad (nt,), s2, L, c).  Raises LinAlgError when K is not positive definite and
+    ValueError when q is not positive and finite (constant data)."""
+    X = np.asarray(X, dtype=np.float64)
+    r = np.asarray(y, dtype=np.float64).ravel()
+    N = r.size
+    D = X[:, :, None] - X[:, None, :]
+    ρ = np.sqrt((D * D).sum(0))
+    np.fill_diagonal(ρ, 0.0)
+    K = ψ(ρ) + σn2 * np.eye(N)
+    L = np.linalg.cholesky(K)
+    c = np.linalg.solve(L.T, np.linalg.solve(L, r))
+    q = float(r @ c)
+    if not (q > 0.0 and math.isfinite(q)):
+        raise ValueError("profiled likelihood: rᵀK⁻¹r is not positive and finite (constant data)")
+    Kinv = np.linalg.solve(L.T, np.linalg.solve(L, np.eye(N)))
+    dK = _dpsi_dtheta(ψ, ρ)
+    for t in range(dK.shape[0]):
+        np.fill_diagonal(dK[t], 0.0)
+    grad = np.array([N / (2.0 * q) * (c @ dK[t] @ c) - 0.5 * np.sum(Kinv * dK[t]) for t in range(dK.shape[0])])
+    ll = -0.5 * N * math.log(q / N) - float(np.log(np.diag(L)).sum()) - 0.5 * N * (1.0 + math.log(2.0 * math.pi))
+    return dict(ll=ll, grad=grad, s2=q / N, L=L, c=c)
+
+
+def gp_fit_batch(s, thetas, want_fit=False, profile=False):
     """Refit the base GP of `s` at each hyperparameter vector on the device (mrbo_gp_fit_theta).
 
     `thetas` is (P,) -- lengthscales -- or (P, nt) with nt = len(s.ψ.θ).  Returns dict(ll, grad
-    (P, nt), dll (= grad[:, 0]), status[, L (N×N×P), c (N×P)]); status 1 = PosDefException."""
+    (P, nt), dll (= grad[:, 0]), status[, L (N×N×P), c (N×P)]); status 1 = PosDefException.
+    profile=True: the profiled-amplitude likelihood (gp_fit_multi's, S = 1), with s2 (P,) added."""
+    if profile:
+        r = gp_fit_multi([s], np.asarray(thetas, dtype=np.float64)[None], want_fit, profile=True)
+        out = {k: v[0] for k, v in r.items()}
+        out["dll"] = out["dll"].copy()
+        return out
     L = _lib.load()
     th = np.asarray(thetas, dtype=np.float64)
     th = np.ascontiguousarray(th.reshape(th.shape[0], -1) if th.ndim > 1 else th.reshape(-1, 1))
@@ -75,9 +136,12 @@ def check_fit_batch(surs):
     return d, N, _nt(s0)
 
 
-def gp_fit_multi(surs, thetas, want_fit=False):
+def gp_fit_multi(surs, thetas, want_fit=False, profile=False):
     """gp_fit_batch for S surrogates with P hyperparameter vectors each, in one launch
     (mrbo_gp_fit_multi): block q is bit-identical to gp_fit_batch(surs[q], thetas[q]).
+    profile=True evaluates the profiled-amplitude likelihood instead (mrbo_gp_fit_profile_multi:
+    ll and grad are ll_p and ∂ll_p of profile_log_likelihood_host, s2 (S, P) is added to the dict,
+    status 2 marks constant data; L and c are the plain call's).
 
     `thetas` is (S, P) -- lengthscales -- or (S, P, nt).  The surrogates share d, N, the kernel
     family and σn2 (ValueError otherwise).  Returns dict(ll (S, P), grad (S, P, nt), dll
@@ -102,9 +166,16 @@ def gp_fit_multi(surs, thetas, want_fit=False):
     Lo = np.zeros((S, P, n, n)) if want_fit else None      # N×N×P×S column-major
     co = np.zeros((S, P, n)) if want_fit else None
     vp = lambda a: ctypes.c_void_p(a.ctypes.data) if a is not None else None
-    _lib.check(L.mrbo_gp_fit_multi(sds, S, P, nt, vp(th), vp(ll), vp(grad), vp(st), vp(Lo), vp(co),
-                                   _lib.MRBO_FLAG_HOST_POINTERS, None))
+    if profile:
+        s2 = np.zeros((S, P))
+        _lib.check(L.mrbo_gp_fit_profile_multi(sds, S, P, nt, vp(th), vp(ll), vp(grad), vp(s2), vp(st), vp(Lo), vp(co),
+                                               _lib.MRBO_FLAG_HOST_POINTERS, None))
+    else:
+        _lib.check(L.mrbo_gp_fit_multi(sds, S, P, nt, vp(th), vp(ll), vp(grad), vp(st), vp(Lo), vp(co),
+                                       _lib.MRBO_FLAG_HOST_POINTERS, None))
     out = dict(ll=ll, grad=grad, dll=grad[:, :, 0].copy(), status=st)
+    if profile:
+        out["s2"] = s2
     if want_fit:
         out["L"], out["c"] = Lo.transpose(0, 3, 2, 1), co.transpose(0, 2, 1)
     return out
@@ -323,7 +394,8 @@ def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1
     return np.array(x), f, np.array(g), it
 
 
-def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, iterations=30, history=10):
+def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, iterations=30, history=10,
+                      profile_amplitude=False):
     """The S minimisations of optimize_multi as ONE device-resident call (mrbo_gp_optimize_multi):
     the data sets are staged once, and every line-search round -- one fit launch of grid (12, S) and
     one step kernel -- follows the last on the stream without a host round trip.  Problem q starts
@@ -333,7 +405,9 @@ def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, ite
 
     Returns dict(theta (S, nt), neg_log_likelihood (S,), gradient (S, nt), iterations (S,), rounds
     -- fit launches made, the start's included --, stopped_at -- the round after which no problem
-    ran, 1 + max(iterations))."""
+    ran, 1 + max(iterations)).  profile_amplitude=True minimises −ll_p, the profiled-amplitude
+    likelihood (mrbo_gp_optimize_profile_multi; its specification is lbfgs_scalar driven by
+    gp_fit_batch(·, profile=True)), and adds s2 (S,): the amplitude ŝ² at theta."""
     surs = list(surs)
     d, n, nt = check_fit_batch(surs)
     if lowerbounds is None or upperbounds is None:
@@ -361,22 +435,35 @@ def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, ite
     its = np.zeros(S, dtype=np.int32)
     res = (ctypes.c_int32 * 2)()
     vp = lambda a: ctypes.c_void_p(a.ctypes.data)
-    _lib.check(L.mrbo_gp_optimize_multi(sds, S, nt, vp(th0), vp(lo), vp(hi), ctypes.byref(opts), vp(th), vp(f), vp(g),
-                                        vp(its), res, _lib.MRBO_FLAG_HOST_POINTERS, None))
-    return dict(theta=th, neg_log_likelihood=f, gradient=g, iterations=its, rounds=int(res[0]),
-                stopped_at=int(res[1]))
+    if profile_amplitude:
+        s2 = np.zeros(S)
+        _lib.check(L.mrbo_gp_optimize_profile_multi(sds, S, nt, vp(th0), vp(lo), vp(hi), ctypes.byref(opts), vp(th),
+                                                    vp(f), vp(g), vp(s2), vp(its), res,
+                                                    _lib.MRBO_FLAG_HOST_POINTERS, None))
+    else:
+        _lib.check(L.mrbo_gp_optimize_multi(sds, S, nt, vp(th0), vp(lo), vp(hi), ctypes.byref(opts), vp(th), vp(f),
+                                            vp(g), vp(its), res, _lib.MRBO_FLAG_HOST_POINTERS, None))
+    out = dict(theta=th, neg_log_likelihood=f, gradient=g, iterations=its, rounds=int(res[0]),
+               stopped_at=int(res[1]))
+    if profile_amplitude:
+        out["s2"] = s2
+    return out
 
 
-def optimize(s, lowerbounds, upperbounds, iterations=30, device=False):
+def optimize(s, lowerbounds, upperbounds, iterations=30, device=False, profile_amplitude=False):
     """optimize!(s; lowerbounds, upperbounds) (radial_basis_surrogates.jl:805-829): maximise the
     log likelihood over the kernel hyperparameters (ℓ; Periodic ℓ and p) within the box, then
     set_kernel! at the optimum.  device=True runs the minimisation as one device-resident call
-    (gp_optimize_multi with S = 1)."""
+    (gp_optimize_multi with S = 1).  profile_amplitude=True maximises the profiled-amplitude
+    likelihood instead (on either path); a standardised surrogate (Surrogate(standardize=True))
+    always does, its amplitude being part of the fit."""
+    profile_amplitude = bool(profile_amplitude) or bool(getattr(s, "standardize", False))
     if device:
-        return optimize_multi([s], lowerbounds, upperbounds, iterations, device=True)[0]
+        return optimize_multi([s], lowerbounds, upperbounds, iterations, device=True,
+                              profile_amplitude=profile_amplitude)[0]
 
     def fg(T):
-        r = gp_fit_batch(s, T)
+        r = gp_fit_batch(s, T, profile=profile_amplitude)
         f = np.where(r["status"] == 0, -r["ll"], np.nan)
         return f, -r["grad"]
 
@@ -386,18 +473,23 @@ def optimize(s, lowerbounds, upperbounds, iterations=30, device=False):
     return dict(theta=θ, neg_log_likelihood=f, gradient=g, iterations=it)
 
 
-def optimize_multi(surs, lowerbounds, upperbounds, iterations=30, device=False):
+def optimize_multi(surs, lowerbounds, upperbounds, iterations=30, device=False, profile_amplitude=False):
     """optimize for the surrogates of k lockstep trials: the minimisations advance together, and
     each round's evaluations -- one line search per surrogate still running -- are ONE
     gp_fit_multi launch instead of one launch per surrogate.  Every surrogate ends with the θ,
     objective, gradient and iteration count optimize alone gives it.  Returns optimize's dict per
     surrogate.  device=True runs the whole minimisation in one device-resident call
-    (gp_optimize_multi: no host round trip per round) and then set_kernel on the host as before."""
+    (gp_optimize_multi: no host round trip per round) and then set_kernel on the host as before.
+    profile_amplitude=True maximises the profiled-amplitude likelihood instead (on either path)."""
     surs = list(surs)
     check_fit_batch(surs)
+    std = [bool(getattr(s, "standardize", False)) for s in surs]
+    if any(std) and not all(std):
+        raise ValueError("optimize_multi: standardised and plain surrogates in one batch")
+    profile_amplitude = bool(profile_amplitude) or std[0]   # a standardised surrogate fits its amplitude
     from .kernels import set_hyperparameters
     if device:
-        r = gp_optimize_multi(surs, None, lowerbounds, upperbounds, iterations)
+        r = gp_optimize_multi(surs, None, lowerbounds, upperbounds, iterations, profile_amplitude=profile_amplitude)
         out = []
         for q, s in enumerate(surs):
             θ = r["theta"][q].copy()
@@ -407,7 +499,7 @@ def optimize_multi(surs, lowerbounds, upperbounds, iterations=30, device=False):
         return out
 
     def fg_multi(idx, T):
-        r = gp_fit_multi([surs[i] for i in idx], T)
+        r = gp_fit_multi([surs[i] for i in idx], T, profile=profile_amplitude)
         f = np.where(r["status"] == 0, -r["ll"], np.nan)
         return f, -r["grad"]
 
