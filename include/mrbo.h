@@ -551,7 +551,11 @@ double mrbo_last_gp_fit_ms(void);
  * launch, a surrogate batch launches ⌈info[1]/S⌉ × S);
  * info[8] = restart table (1: the step-0 evaluation at x0 and the factor of its draw run once per
  * restart and every sample reads them; 0: every trajectory runs them -- MRBO_RESTART_TABLES=0 in the
- * environment at plan creation, the half-wave kernel, N > 64).  Writes min(n, 9). */
+ * environment at plan creation, the half-wave kernel, N > 64);
+ * info[9] = fused Newton iteration of the inner solve (1: an accepted line-search trial that does not
+ * end the iteration goes on to its gradient and Hessian in the same evaluation call; 0: the two-call
+ * loop -- MRBO_NEWTON_FUSED=0 in the environment at plan creation, the half-wave kernel, N > 64);
+ * results are bit-identical either way.  Writes min(n, 10). */
 int mrbo_plan_info(const mrbo_plan_t* plan, int32_t* info, int32_t n);
 
 /* Work order of the plan's later mrbo_simulate_mc / mrbo_simulate_ghq launches (no reference

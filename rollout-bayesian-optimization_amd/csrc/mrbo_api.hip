@@ -72,6 +72,7 @@ struct mrbo_plan {
   double* dytab = nullptr;  // batched starts: the launch's Y0(x_start) table (square layout, ytab_kernel)
   double* drtab = nullptr;  // the launch's restart table (KParams::rtab), R·S rows; null: step 0 in place
   int rtab_wg = 0;          // its writer workgroups per surrogate in the ytab_kernel launch
+  int newton_fused = 0;     // KParams::newton_fused of the plan's launches
   double* dkxb = nullptr;   // batched starts, packed layouts: global start tables (start_tables_kernel)
   double* dgtab = nullptr;
   SurTab* dstab = nullptr;  // S > 1: the per-surrogate table (KParams::stab); dX0 ... dgtab hold S blocks
@@ -408,6 +409,7 @@ static void fill_common(const mrbo_plan_t* P, KParams& kp) {
   kp.cost_tab = P->dcost;
   kp.stab = P->dstab;
   kp.S = P->S;
+  kp.newton_fused = P->newton_fused;
 }
 
 // Device buffers of plan-less calls (mrbo_gp_fit: staging and the tile kernel's workspace) are
@@ -800,6 +802,12 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
   const bool use_rtab = ks.square && P->spec != 2 && p->R > 0 && !(rt && rt[0] == '0');
   // a wave per restart, in workgroups of the rollout launch's shape
   P->rtab_wg = use_rtab ? std::min(256, (p->R + P->wpg - 1) / P->wpg) : 0;
+  // The fused Newton iteration (an accepted trial's gradient and Hessian in the trial's own
+  // evaluation call): the same kernels as the restart table.  The half-wave kernel and the N > 64
+  // layouts are built with the two-call loop only.  MRBO_NEWTON_FUSED=0 keeps the two-call loop
+  // everywhere (A/B runs and tests); mrbo_plan_info reports which it is
+  const char* nfz = getenv("MRBO_NEWTON_FUSED");
+  P->newton_fused = (ks.square && P->spec != 2 && !(nfz && nfz[0] == '0')) ? 1 : 0;
   // packed layouts: the start tables live in global memory (no LDS, no occupancy cost)
   if (!ks.square && P->xs_lds && ns <= 64) P->batch = 1;
   if (!waves0 ||
@@ -2081,9 +2089,9 @@ int mrbo_plan_order_longest_first(mrbo_plan_t* P, const int64_t* evals, int32_t*
 
 int mrbo_plan_info(const mrbo_plan_t* P, int32_t* info, int32_t n) {
   if (!P || !info || n < 0) return fail(MRBO_ERR_ARG, "bad arguments");
-  const int32_t v[9] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6, P->S,
-                        P->drtab ? 1 : 0};
-  for (int i = 0; i < n && i < 9; ++i) info[i] = v[i];
+  const int32_t v[10] = {P->RPL, P->blocks, P->wpg, P->batch, P->spec, (int32_t)P->smem, P->fx ? 4 : 6, P->S,
+                         P->drtab ? 1 : 0, P->newton_fused};
+  for (int i = 0; i < n && i < 10; ++i) info[i] = v[i];
   return MRBO_OK;
 }
 

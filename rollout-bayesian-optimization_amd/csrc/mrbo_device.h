@@ -142,7 +142,15 @@ struct KParams {
   // rtab_wg further workgroups of the ytab_kernel launch, read by trajectory() at k = 0
   double* rtab;         // [R·S][rtab_stride(d, NR)]
   int rtab_wg;
+  // Fused Newton iteration (square full-wave layout): an accepted line-search trial that does not
+  // end the iteration goes on to its gradient columns, the projected-gradient test and the BACK
+  // part in the same evaluate() call.  0: the two-call loop (VALUE, then GRADC + BACK)
+  int newton_fused;
 };
+
+// what a Newton line-search evaluation ran besides its first part (evaluate()'s return value)
+enum { EVR_BACK = 1,    // the BACK part (backward product, Hα)
+       EVR_GRAD = 2 };  // the gradient columns after the VALUE part (fused Newton iteration)
 
 // one row of KParams::rtab: w (NR doubles, one per lane), then the header
 //   [σ², μ, G00, σ, factor failed (0 / 1), ∇μ (d), ∇σ (d), packed factor of Dk(0) − G ((d+1)(d+2)/2)]

@@ -567,18 +567,40 @@ __device__ __forceinline__ void gl_block(double (&acc)[K], const double (&v)[K],
 template <int D, int RPL, int HW>
 __device__ __forceinline__ bool newton_pg_ok(WaveCtx<D, RPL, HW>& W, const KParams& kp);
 
+// The Newton iteration's state around a VALUE evaluation (newton below): what the decision code
+// that follows the evaluation (newton_after_value) reads and updates, and its outcome.
+struct NewtonState {
+  double f, ft, dec, t;   // f(x), f(x_t), gᵀ(x_t − x) and the step length of the trial
+  int it, ls;             // iterations taken, backtracks of this direction
+  int st;                 // status bits found (σ² < 0)
+  bool trial;             // the evaluation is a line-search trial (else the start point's value)
+  int why;                // NT_*
+};
+enum { NT_STOP = 0,        // the iteration ends here
+       NT_BACKTRACK = 1,   // projected Armijo failed: the caller halves the step (t is updated)
+       NT_CONTINUE = 2 };  // the gradient at x = U_NX is needed
+template <int D, int RPL, int HW>
+__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, NewtonState& ns);
+
 // ================================================================================
 // eval(fs, x, θ; fantasy_index = S)  -- radial_basis_surrogates.jl:482-581
 //   x is read from U[U_X].  Results land in U (lane-uniform) and `lr` (per lane).
 // ================================================================================
 // back_after (GRAD / GRADC / GSTART of the Newton iteration): the projected-gradient test runs
 // here and, when the step continues, the BACK part (backward product, Hα) follows in the same
-// call with the forward state still in registers.  Returns 1 when that BACK part ran.
-template <int D, int RPL, int HW>
+// call with the forward state still in registers.  Returns EVR_BACK when that BACK part ran.
+// nt (the VALUE evaluations of the Newton iteration on the square full-wave layout): the iteration's
+// decision code (newton_after_value) runs here, right after the σ / EI part, and leaves its outcome
+// in nt->why.  With kp.newton_fused, an outcome NT_CONTINUE does not return: the call goes on with
+// the GRADC evaluation at the same x that the caller would issue next, the projected-gradient test
+// and the BACK part (back_after) -- the same code, instantiated once more with INNER -- and returns
+// EVR_GRAD as well.
+template <int D, int RPL, int HW, bool INNER = false>
 __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int mode, LaneRes<D, RPL, HW>& lr,
-                                        int kst = 0, bool back_after = false) {
+                                        int kst = 0, bool back_after = false, NewtonState* nt = nullptr) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1, BS = Ly::BS, NR = Ly::NR;
+  constexpr bool FUSABLE = Ly::SQ && HW == 1;
   // Opaque copy of the lane index: keeps the per-lane LDS/global addresses derived from it
   // inside this evaluation instead of being hoisted (and held live in VGPRs) across the
   // caller's Newton / horizon loops -- the difference between 1 and 3-4 waves per SIMD.
@@ -966,7 +988,21 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     U[Ly::U_SC + SC_GSIGTH] = e.gsigth;
     U[Ly::U_SC + SC_FMIN] = fmin;
   }
-  if (mode == EV_VALUE) { wave_sync(); STAMP(W, 4); return 0; }
+  if (mode == EV_VALUE) {
+    wave_sync();
+    STAMP(W, 4);
+    if constexpr (FUSABLE) {
+      if (nt != nullptr) {
+        nt->why = newton_after_value<D, RPL, HW>(W, kp, S, *nt);
+        if (nt->why != NT_CONTINUE || !kp.newton_fused) return 0;
+        // the iteration continues at this x: GRADC, the projected-gradient test and BACK here, in
+        // an instantiation of their own (mode is a compile-time constant in it, and a backward
+        // branch into the code above would make this body a loop, whose hoisted invariants spill)
+        if constexpr (!INNER) return EVR_GRAD | evaluate<D, RPL, HW, true>(W, kp, S, EV_GRADC, lr, kst, true);
+      }
+    }
+    return 0;
+  }
   isig_f = isig;
   e_f = e;
   } else {   // GRADC: σ and the EI partials of the VALUE pass at this point
@@ -1205,7 +1241,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   }
   wave_sync();
   STAMP(W, 7);
-  return 1;
+  return EVR_BACK;
 }
 
 // ================================================================================
@@ -1602,6 +1638,56 @@ __device__ __forceinline__ bool tight_certified(WaveCtx<D, RPL, HW>& W, const KP
   return (fabs(gm) * bmu + bsig) * isc + add <= thr;
 }
 
+// The Newton iteration's decision code after a VALUE evaluation at U_X (newton below), whose
+// results are in U: the start point's value, or a line-search trial -- projected Armijo test,
+// accept (U_NX moves, ‖Δx‖∞ and |Δf| tests, ++it) -- then the iteration limit, the NaN exit and the
+// two gradient certificates.  One inlined copy per kernel: inside evaluate() on the square
+// full-wave layout (evaluate's nt), in newton() elsewhere.
+template <int D, int RPL, int HW>
+__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, NewtonState& ns) {
+  using Ly = Lay<D, RPL, HW>;
+  double* U = W.U;
+  const int lane = W.ln();
+  if (U[Ly::U_SC + SC_VAR] < 0.0) ns.st |= 1;
+  const double fe = -U[Ly::U_SC + SC_ALPHA];
+  if (ns.trial) {
+    ns.ft = fe;
+    if (!(ns.ft == ns.ft && ns.ft <= ns.f + 1e-4 * ns.dec)) {   // projected Armijo, backtrack
+      ++ns.ls;
+      if (ns.ls >= kp.max_ls) return NT_STOP;      // no acceptable step
+      ns.t *= 0.5;
+      return NT_BACKTRACK;
+    }
+    // accept x_t: lane a < D moves its coordinate; ‖Δx‖∞ from the lanes' |Δx_a| (max: order-free)
+    const int ca = lane < D ? lane : 0;
+    const double xt = U[Ly::U_X + ca];
+    const double dxa = fabs(xt - U[Ly::U_NX + ca]);
+    double dx = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) dx = fmax(dx, hw_readlane_d<HW>(dxa, a, W.half));
+    const double df = fabs(ns.ft - ns.f);
+    wave_sync();
+    if (lane < D) U[Ly::U_NX + lane] = xt;
+    wave_sync();
+    ns.f = ns.ft;
+    ++ns.it;
+    if (dx <= KCV(XTOL) || df <= KCV(FTOL) * fabs(ns.f)) return NT_STOP;
+  } else {
+    ns.f = fe;
+  }
+  STAMP(W, 19);
+  // decision point at x = U_NX (= U_X), whose VALUE evaluation is in U
+  if (ns.it >= kp.max_iters) return NT_STOP;
+  if (ns.f != ns.f) return NT_STOP;
+  if (grad_certified<D, RPL, HW>(W, kp)) return NT_STOP;     // ‖∇α‖ ≤ g_tol guaranteed: stationary
+  if (kp.gcert_sig > 0.0 &&
+      tight_certified<D, RPL, HW, true>(W, kp, S, U[Ly::U_SC + SC_GMU], U[Ly::U_SC + SC_GSIG], U[Ly::U_SC + SC_SIG],
+                                    U[Ly::U_SC + SC_ISIG], kp.cost ? U[Ly::U_SC + SC_ARAW] : 0.0))
+    return NT_STOP;
+  STAMP(W, 20);
+  return NT_CONTINUE;
+}
+
 // Deterministic projected Newton on f = -α over the box, from start k.
 // A state machine around ONE evaluate() call site.  Work is lazy, decisions are not: every
 // point gets a value-only evaluation; the gradient columns are completed (GRADC) only where
@@ -1633,16 +1719,42 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   // stop the iteration, so it begins with the gradient at x_start
   // (GSTART takes the base forward product from the square layout's per-workgroup tables; the
   // packed layouts evaluate the gradient at the start point in full)
-  int phase = have_f0 ? P_GRAD : P_VAL, mode = have_f0 ? (Ly::SQ ? EV_GSTART : EV_GRAD) : EV_VALUE, it = 0, ls = 0;
-  double f = have_f0 ? f0 : 0.0, ft = 0.0, t = 1.0, dec = 0.0;
+  int phase = have_f0 ? P_GRAD : P_VAL, mode = have_f0 ? (Ly::SQ ? EV_GSTART : EV_GRAD) : EV_VALUE;
+  // square full-wave layout: the decision code after a VALUE evaluation runs inside the evaluation
+  // call, which with kp.newton_fused goes on to GRADC + BACK where the iteration continues
+  constexpr bool FUSABLE = Ly::SQ && HW == 1;
+  NewtonState ns;
+  ns.f = have_f0 ? f0 : 0.0;
+  ns.ft = 0.0;
+  ns.t = 1.0;
+  ns.dec = 0.0;
+  ns.it = 0;
+  ns.ls = 0;
+  ns.st = 0;
+  ns.why = NT_STOP;
   for (;;) {
+    ns.trial = (phase == P_TRIAL);
     // P_GRAD: GRAD + BACK in one evaluation call (evaluate back_after)
-    const int back = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, phase == P_GRAD);
+    const int ran = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, phase == P_GRAD, FUSABLE ? &ns : nullptr);
     if (mode == EV_VALUE) ++nevals.value;
     else if (mode == EV_GRADC || mode == EV_GRAD || mode == EV_GSTART) ++nevals.grad;
     else ++nevals.hess;
+    if (mode == EV_VALUE) {   // the start point (P_VAL) or a line-search trial (P_TRIAL)
+      if constexpr (!FUSABLE) ns.why = newton_after_value<D, RPL, HW>(W, kp, S, ns);
+      if (ns.why == NT_STOP) break;
+      if (ns.why == NT_BACKTRACK) {
+        ns.dec = newton_trial_point<D, RPL, HW>(W, ns.t);
+        continue;
+      }
+      phase = P_GRAD;
+      if (!(ran & EVR_GRAD)) {   // the two-call loop: the gradient columns at x in a call of their own
+        mode = EV_GRADC;
+        continue;
+      }
+      ++nevals.grad;             // they ran in the same call, with the projected-gradient test
+    }
     if (phase == P_GRAD) {   // the projected-gradient test ran inside the evaluation
-      if (!back) break;                   // stationary
+      if (!(ran & EVR_BACK)) break;       // stationary
       ++nevals.hess;                      // the BACK part (Hα) ran in the same call
       phase = P_HESS;
     }
@@ -1651,58 +1763,18 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
       const bool go = newton_direction<D, RPL, HW>(W, kp);
       STAMP(W, 13);
       if (!go) break;
-      t = 1.0;
-      ls = 0;
-      dec = newton_trial_point<D, RPL, HW>(W, t);
+      ns.t = 1.0;
+      ns.ls = 0;
+      ns.dec = newton_trial_point<D, RPL, HW>(W, ns.t);
       STAMP(W, 14);
       phase = P_TRIAL;
       mode = EV_VALUE;
       continue;
     }
-    // a VALUE evaluation: the start point (P_VAL) or a line-search trial (P_TRIAL)
-    if (U[Ly::U_SC + SC_VAR] < 0.0) st |= 1;
-    const double fe = -U[Ly::U_SC + SC_ALPHA];
-    if (phase == P_TRIAL) {
-      ft = fe;
-      if (!(ft == ft && ft <= f + 1e-4 * dec)) {   // projected Armijo, backtrack
-        ++ls;
-        if (ls >= kp.max_ls) break;                // no acceptable step
-        t *= 0.5;
-        dec = newton_trial_point<D, RPL, HW>(W, t);
-        continue;
-      }
-      // accept x_t: lane a < D moves its coordinate; ‖Δx‖∞ from the lanes' |Δx_a| (max: order-free)
-      const int ca = lane < D ? lane : 0;
-      const double xt = U[Ly::U_X + ca];
-      const double dxa = fabs(xt - U[Ly::U_NX + ca]);
-      double dx = 0.0;
-#pragma unroll
-      for (int a = 0; a < D; ++a) dx = fmax(dx, hw_readlane_d<HW>(dxa, a, W.half));
-      const double df = fabs(ft - f);
-      wave_sync();
-      if (lane < D) U[Ly::U_NX + lane] = xt;
-      wave_sync();
-      f = ft;
-      ++it;
-      if (dx <= KCV(XTOL) || df <= KCV(FTOL) * fabs(f)) break;
-    } else {
-      f = fe;
-    }
-    STAMP(W, 19);
-    // decision point at x = U_NX (= U_X), whose VALUE evaluation is in U
-    if (it >= kp.max_iters) break;
-    if (f != f) break;
-    if (grad_certified<D, RPL, HW>(W, kp)) break;     // ‖∇α‖ ≤ g_tol guaranteed: stationary
-    if (kp.gcert_sig > 0.0 &&
-        tight_certified<D, RPL, HW, true>(W, kp, S, U[Ly::U_SC + SC_GMU], U[Ly::U_SC + SC_GSIG], U[Ly::U_SC + SC_SIG],
-                                      U[Ly::U_SC + SC_ISIG], kp.cost ? U[Ly::U_SC + SC_ARAW] : 0.0))
-      break;
-    STAMP(W, 20);
-    phase = P_GRAD;
-    mode = EV_GRADC;
   }
+  st |= ns.st;
   wave_sync();
-  return f;
+  return ns.f;
 }
 
 // Workgroup prologue (kp.batch): base kernel rows of the clamped start points and the squared

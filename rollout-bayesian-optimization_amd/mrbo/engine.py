@@ -467,10 +467,13 @@ class RolloutPlan:
         """Launch geometry: rows per lane, workgroups, waves per workgroup, batched start values,
         specialised kernel, LDS bytes per workgroup, fantasy capacity of the kernel unit (FMAX), base
         surrogates S (1: a plain plan), restart table (1: step 0 of a trajectory runs once per restart,
-        0: in every trajectory -- MRBO_RESTART_TABLES=0, the half-wave kernel, N > 64)."""
-        v = (ctypes.c_int32 * 9)()
-        _lib.check(self.lib.mrbo_plan_info(self.handle, v, 9))
-        keys = ("rpl", "blocks", "waves_per_group", "batch", "spec", "lds_bytes", "fmax", "S", "restart_tables")
+        0: in every trajectory -- MRBO_RESTART_TABLES=0, the half-wave kernel, N > 64), fused Newton
+        iteration (1: an accepted line-search trial goes on to its gradient and Hessian in the same
+        evaluation call, 0: the two-call loop -- MRBO_NEWTON_FUSED=0, the half-wave kernel, N > 64)."""
+        v = (ctypes.c_int32 * 10)()
+        _lib.check(self.lib.mrbo_plan_info(self.handle, v, 10))
+        keys = ("rpl", "blocks", "waves_per_group", "batch", "spec", "lds_bytes", "fmax", "S", "restart_tables",
+                "newton_fused")
         return dict(zip(keys, (int(x) for x in v)))
 
 

@@ -6,6 +6,8 @@ samples, caller-owned containers overwritten in place, ExpectedTrajectoryOutput 
 ``simulate_trajectory_mc_batch`` is the MI355X-shaped entry: R restarts × M samples in one
 launch, outputs left on the device.
 """
+import hashlib
+
 import numpy as np
 
 from . import _lib
@@ -15,12 +17,25 @@ from .trajectory import ExpectedTrajectoryOutput
 _PLANS = {}
 
 
+def _state_key(s):
+    """What a plan is built from, by content: id(s) and s.version alone do not identify a surrogate --
+    CPython reuses the id of a freed one, and a fresh surrogate starts at the same version -- so a
+    plan cached for a surrogate that is gone was handed to its successor at the same address (as
+    shim._key, which hashes the arrays for the same reason)."""
+    n = s.observed
+    h = hashlib.blake2b(digest_size=16)
+    for a in (s.X[:, :n], s.L[:n, :n], s.c[:n], s.y[:n]):
+        h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+    return (id(s), s.version, n, h.hexdigest(), s.ψ.kind, float(s.ψ.lengthscale), float(s.ψ.period), float(s.σn2),
+            float(s.fmini()))
+
+
 def _plan_for(s, h, M, R, nstarts, lbs, ubs, theta, device, opts):
     g = s.get_decision_rule()
     opts = dict(opts)
     opts.setdefault("rule", g.rule_id)       # the surrogate's base decision rule (Q12: T.θ)
     opts.setdefault("sigma_tol", g.σtol)
-    key = (id(s), s.version, h, M, R, nstarts, tuple(np.asarray(lbs).ravel()), tuple(np.asarray(ubs).ravel()),
+    key = (_state_key(s), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()), tuple(np.asarray(ubs).ravel()),
            float(theta), device, tuple(sorted(opts.items())))
     p = _PLANS.get(key)
     if p is None:
@@ -62,13 +77,13 @@ def check_surrogate_batch(surrogates):
 
 def _plan_for_multi(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts):
     """_plan_for for a surrogate batch: one RolloutPlan.from_surrogates plan, cached on the
-    surrogates' identities and versions."""
+    surrogates' identities, versions and contents (_state_key)."""
     check_surrogate_batch(ss)
     g = ss[0].get_decision_rule()
     opts = dict(opts)
     opts.setdefault("rule", g.rule_id)
     opts.setdefault("sigma_tol", g.σtol)
-    key = (tuple((id(s), s.version) for s in ss), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()),
+    key = (tuple(_state_key(s) for s in ss), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()),
            tuple(np.asarray(ubs).ravel()), float(theta), device, tuple(sorted(opts.items())))
     p = _PLANS.get(key)
     if p is None:
