@@ -82,7 +82,7 @@ struct mrbo_plan {
                                     // (or the plan's own, mrbo_plan_order_longest_first)
   void* oorder = nullptr;           // mrbo_plan_order_longest_first: keys, ranking, sort scratch, order
   size_t oorder_bytes = 0;
-  const int32_t* skip_active = nullptr;   // set by mrbo_stochastic_solve for its launches only
+  const int32_t* skip_active = nullptr;   // set by the shared ascent (Ascent::run) for its launches only
   int control_variate = 0;  // mrbo_plan_set_control_variate: mrbo_rollout_solve's rows are mrbo_eto_reduce_cv's
   int wpg = 4, blocks = 0;
   size_t smem = 0;
@@ -101,8 +101,9 @@ struct mrbo_plan {
   // MRBO_FLAG_HOST_POINTERS staging: device buffers kept across calls, one slot per staged
   // argument in call order, grown on demand and freed with the plan
   std::vector<std::pair<void*, size_t>> stage;
-  // mrbo_stochastic_solve: the outer ascent's device state (one slot per buffer, grown on demand),
-  // a pinned ring of per-iteration checks read back behind the launches, and its events
+  // mrbo_stochastic_solve, mrbo_rollout_solve: the outer ascent's device state (one slot per buffer,
+  // the SLOT_ names, grown on demand; the pick's and the control variate's buffers behind them), a
+  // pinned ring of per-iteration checks read back behind the launches, and its events
   std::vector<std::pair<void*, size_t>> solve;
   static constexpr int NCHK = 8;
   int32_t* hchk = nullptr;   // pinned, 2 × NCHK: [status bits of the iteration, restarts still active]
@@ -1168,6 +1169,174 @@ static void* solve_slot(mrbo_plan_t* P, size_t k, size_t bytes) {
   return b.first;
 }
 
+// slots of the plan's outer-ascent buffers (mrbo_plan::solve): the ascent's own, then those of the
+// pick and of the control variate
+enum {
+  SLOT_X0, SLOT_RN, SLOT_XSTARTS, SLOT_DUAL, SLOT_ETO, SLOT_ACTIVE, SLOT_VALUES, SLOT_GRAD_X, SLOT_GRAD_THETA,
+  SLOT_STATUS, SLOT_M, SLOT_V, SLOT_CHECK, SLOT_EVALS,
+  SLOT_XNEXT, SLOT_MEAN, SLOT_PICK, SLOT_MEANS, SLOT_NOVEL, SLOT_CV_BASE, SLOT_CV_VALUES, SLOT_CV_GRAD
+};
+
+// what mrbo_stochastic_solve and mrbo_rollout_solve ask of the ascent they share
+struct AscentOpts {
+  const mrbo_solve_opts_t* step;   // optimizer, iterations and step sizes (validated by the caller)
+  const double* dual_y_dx;         // the launches' dual_y_dx (null: none)
+  bool stop_on_bits;               // a status bit ends the ascent
+  bool auto_order;                 // launches after the first: longest first by the first one's work counters
+  bool control_variate;            // every launch is followed by its control launch; rows by mrbo_eto_reduce_cv
+  double* eto;                     // the caller's ETO rows and stop flags (null: the plan's slots)
+  int32_t* active;
+};
+
+// The outer ascent (stochastic_solve, utils.jl:235-265) on the plan's slots: up to `iterations` ×
+// [rollout launch, ETO reduction, optimiser step, check], with no host round trip between them.
+struct Ascent {
+  static constexpr int LAG = 2;
+  mrbo_plan_t* P;
+  hipStream_t st;
+  bool host;   // MRBO_FLAG_HOST_POINTERS
+  // device state after run(): x0 (d×R), the inputs, the ETO rows, the stop flags, the launch outputs
+  // (the control launch's behind them), the checks
+  size_t T = 0, nst = 0, nx = 0;
+  double* x0 = nullptr;
+  const double *rn = nullptr, *xs = nullptr;
+  double* eto = nullptr;
+  int32_t* act = nullptr;
+  double *vals = nullptr, *gx = nullptr, *gt = nullptr, *v0 = nullptr, *g0 = nullptr;
+  int32_t *status = nullptr, *chk = nullptr;
+  int it = 0, stopped_at = 0, bits = 0;   // iterations launched, the first with no restart active, status bits
+
+  // the check of the launches so far into ring slot k, and its copy to the pinned ring
+  int post_check(int k) {
+    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)status, (long long)nst,
+                       (const int*)act, P->p.R * P->S, (int*)chk + 2 * k);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(P->hchk + 2 * k, chk + 2 * k, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+    return MRBO_OK;
+  }
+  int read_check(int j) {   // iteration j ≥ 1 (its slot not yet reused)
+    const int k = (j - 1) % mrbo_plan::NCHK;
+    if (hipEventSynchronize(P->chk_ev[k]) != hipSuccess) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
+    bits |= P->hchk[2 * k];
+    if (P->hchk[2 * k + 1] == 0 && !stopped_at) stopped_at = j;
+    return MRBO_OK;
+  }
+  // the (at most LAG) checks run() left in flight; the caller has synchronised the stream
+  int read_trailing() {
+    for (int j = std::max(1, it - LAG + 1); j <= it; ++j)
+      if (int rc = read_check(j)) return rc;
+    return MRBO_OK;
+  }
+  int run(double* x0s, const double* rnstream, const double* xstarts, const AscentOpts& a);
+};
+
+int Ascent::run(double* x0s, const double* rnstream, const double* xstarts, const AscentOpts& a) {
+  const mrbo_solve_opts_t* o = a.step;
+  const double* dual_y_dx = a.dual_y_dx;
+  const bool moments = o->optimizer != MRBO_OPT_SGA, cv = a.control_variate, auto_order = a.auto_order;
+  const int d = P->d, M = P->p.M, R = P->p.R * P->S, h = P->p.h, W = 2 + 2 * d + 2;   // R·S restarts
+  T = (size_t)M * R;
+  nx = (size_t)d * R;
+  // with the control variate every rollout launch is followed by its horizon-0 control launch: its
+  // status words stand behind the rollout's, so that one check reads both
+  nst = cv ? 2 * T : T;
+  const size_t nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
+  const size_t ndual = (size_t)d * std::max(h, 1) * T;
+  const double sample_size = o->sample_size > 0 ? o->sample_size : (double)M;
+  x0 = host ? (double*)solve_slot(P, SLOT_X0, sizeof(double) * nx) : x0s;
+  rn = host ? (const double*)solve_slot(P, SLOT_RN, sizeof(double) * nrn) : rnstream;
+  xs = host ? (const double*)solve_slot(P, SLOT_XSTARTS, sizeof(double) * nxs) : xstarts;
+  const double* dual =
+      (host && dual_y_dx) ? (const double*)solve_slot(P, SLOT_DUAL, sizeof(double) * ndual) : dual_y_dx;
+  eto = (host || !a.eto) ? (double*)solve_slot(P, SLOT_ETO, sizeof(double) * R * W) : a.eto;
+  act = (host || !a.active) ? (int32_t*)solve_slot(P, SLOT_ACTIVE, sizeof(int32_t) * R) : a.active;
+  vals = (double*)solve_slot(P, SLOT_VALUES, sizeof(double) * T);
+  gx = (double*)solve_slot(P, SLOT_GRAD_X, sizeof(double) * d * T);
+  gt = (double*)solve_slot(P, SLOT_GRAD_THETA, sizeof(double) * T);
+  status = (int32_t*)solve_slot(P, SLOT_STATUS, sizeof(int32_t) * nst);
+  v0 = cv ? (double*)solve_slot(P, SLOT_CV_VALUES, sizeof(double) * T) : nullptr;
+  g0 = cv ? (double*)solve_slot(P, SLOT_CV_GRAD, sizeof(double) * d * T) : nullptr;
+  if (cv && (!v0 || !g0)) return fail(MRBO_ERR_NOMEM, "control-variate buffers");
+  double* dm = moments ? (double*)solve_slot(P, SLOT_M, sizeof(double) * nx) : nullptr;
+  double* dv = moments ? (double*)solve_slot(P, SLOT_V, sizeof(double) * nx) : nullptr;
+  chk = (int32_t*)solve_slot(P, SLOT_CHECK, sizeof(int32_t) * 2 * mrbo_plan::NCHK);
+  if (!x0 || !rn || !xs || (dual_y_dx && !dual) || !eto || !act || !vals || !gx || !gt || !status || !chk ||
+      (moments && (!dm || !dv)))
+    return fail(MRBO_ERR_NOMEM, "outer-ascent buffers");
+  int64_t* evals = auto_order ? (int64_t*)solve_slot(P, SLOT_EVALS, sizeof(int64_t) * NCOUNT * T) : nullptr;
+  if (auto_order && !evals) return fail(MRBO_ERR_NOMEM, "outer-ascent work counters");
+  if (!P->hchk && hipHostMalloc(&P->hchk, sizeof(int32_t) * 2 * mrbo_plan::NCHK) != hipSuccess) {
+    P->hchk = nullptr;
+    return fail(MRBO_ERR_NOMEM, "pinned check ring");
+  }
+  for (auto& e : P->chk_ev)
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (host) {
+    HIP_TRY(hipMemcpyAsync(x0, x0s, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)rn, rnstream, sizeof(double) * nrn, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((void*)xs, xstarts, sizeof(double) * nxs, hipMemcpyHostToDevice, st));
+    if (dual_y_dx) HIP_TRY(hipMemcpyAsync((void*)dual, dual_y_dx, sizeof(double) * ndual, hipMemcpyHostToDevice, st));
+  }
+  // every restart starts active (stochastic_solve's loop runs until its eswavs break); the
+  // moment estimates of Adam / BoxAdam start at zero
+  hipLaunchKernelGGL(fill_int_kernel, dim3((R + 63) / 64), dim3(64), 0, st, (int*)act, R, 1);
+  if (moments) {
+    HIP_TRY(hipMemsetAsync(dm, 0, sizeof(double) * nx, st));
+    HIP_TRY(hipMemsetAsync(dv, 0, sizeof(double) * nx, st));
+  }
+  // A restart that eswavs has stopped keeps its x0, so its trajectories (the control launch's too)
+  // would reproduce the outputs of its last launch bit for bit: the later launches skip them
+  // (kp.skip_active), and its outputs and ETO row stay those of its last launch
+  struct SkipGuard {
+    mrbo_plan_t* P;
+    ~SkipGuard() { P->skip_active = nullptr; }
+  } guard{P};
+  P->skip_active = act;
+  // auto_order: the launches after the first take their trajectories longest first by the first
+  // launch's work counters (mrbo_plan_order_longest_first: the launch's idle tail, C3 7.0 → 1.2 %);
+  // the plan's order is restored on return
+  struct OrderGuard {
+    mrbo_plan_t* P;
+    const int32_t* saved;
+    ~OrderGuard() { P->order = saved; }
+  } oguard{P, P->order};
+  // The iterations follow each other on the stream without a host round trip.  Behind them the
+  // host reads iteration j's check (status bits, restarts still active) LAG iterations later: once
+  // every restart has stopped, the launches already queued find x0 unchanged and reproduce the
+  // same trajectories and ETO rows bit for bit, so stopping a few iterations late changes no output.
+  int rc = MRBO_OK;
+  while (it < o->iterations && !stopped_at && !(a.stop_on_bits && bits)) {
+    ++it;
+    rc = mrbo_simulate_mc(P, x0, rn, xs, dual, nullptr, vals, gx, gt, status, nullptr, nullptr,
+                          (auto_order && it == 1) ? evals : nullptr, 0, st);
+    if (rc != MRBO_OK) return rc;
+    if (auto_order && it == 1) {
+      rc = mrbo_plan_order_longest_first(P, evals, nullptr, st);
+      if (rc != MRBO_OK) return rc;
+    }
+    if (cv) {
+      rc = mrbo_simulate_control(P, x0, rn, xs, v0, g0, status + T, 0, st);
+      if (rc != MRBO_OK) return rc;
+      rc = mrbo_eto_reduce_cv(P, x0, vals, gx, gt, v0, g0, eto, nullptr, 0, st);
+    } else {
+      rc = mrbo_eto_reduce(P, vals, gx, gt, eto, 0, st);
+    }
+    if (rc != MRBO_OK) return rc;
+    if (o->optimizer == MRBO_OPT_SGA)
+      rc = mrbo_sga_step(P, eto, x0, act, sample_size, o->eta, 0, st);
+    else if (o->optimizer == MRBO_OPT_ADAM)
+      rc = mrbo_adam_step(P, eto, x0, act, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
+    else
+      rc = mrbo_box_adam_step(P, eto, x0, act, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
+    if (rc != MRBO_OK) return rc;
+    const int k = (it - 1) % mrbo_plan::NCHK;
+    if ((rc = post_check(k)) != MRBO_OK) return rc;
+    HIP_TRY(hipEventRecord(P->chk_ev[k], st));
+    if (it > LAG && (rc = read_check(it - LAG)) != MRBO_OK) return rc;
+  }
+  return MRBO_OK;
+}
+
 int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, const double* xstarts,
                           const double* dual_y_dx, const mrbo_solve_opts_t* o, double* eto, int32_t* active,
                           int32_t* result, uint32_t flags, void* stream) {
@@ -1181,115 +1350,22 @@ int mrbo_stochastic_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, c
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   hipStream_t st = (hipStream_t)stream;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
-  const int d = P->d, M = P->p.M, R = P->p.R * P->S, h = P->p.h, W = 2 + 2 * d + 2;   // R·S restarts
-  const size_t T = (size_t)M * R;
-  const size_t nx = (size_t)d * R, nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
-  const size_t ndual = (size_t)d * std::max(h, 1) * T;
-  const double sample_size = o->sample_size > 0 ? o->sample_size : (double)M;
-  // device state: x0 (d×R), the launch outputs, the ETO rows, the stop flags, Adam's moments, the checks
-  double* dx0 = host ? (double*)solve_slot(P, 0, sizeof(double) * nx) : x0s;
-  const double* drn = host ? (const double*)solve_slot(P, 1, sizeof(double) * nrn) : rnstream;
-  const double* dxs = host ? (const double*)solve_slot(P, 2, sizeof(double) * nxs) : xstarts;
-  const double* ddual = (host && dual_y_dx) ? (const double*)solve_slot(P, 3, sizeof(double) * ndual) : dual_y_dx;
-  double* deto = (host || !eto) ? (double*)solve_slot(P, 4, sizeof(double) * R * W) : eto;
-  int32_t* dact = (host || !active) ? (int32_t*)solve_slot(P, 5, sizeof(int32_t) * R) : active;
-  double* dvals = (double*)solve_slot(P, 6, sizeof(double) * T);
-  double* dgx = (double*)solve_slot(P, 7, sizeof(double) * d * T);
-  double* dgt = (double*)solve_slot(P, 8, sizeof(double) * T);
-  int32_t* dst = (int32_t*)solve_slot(P, 9, sizeof(int32_t) * T);
-  double* dm = o->optimizer == MRBO_OPT_ADAM ? (double*)solve_slot(P, 10, sizeof(double) * nx) : nullptr;
-  double* dv = o->optimizer == MRBO_OPT_ADAM ? (double*)solve_slot(P, 11, sizeof(double) * nx) : nullptr;
-  int32_t* dchk = (int32_t*)solve_slot(P, 12, sizeof(int32_t) * 2 * mrbo_plan::NCHK);
-  if (!dx0 || !drn || !dxs || (dual_y_dx && !ddual) || !deto || !dact || !dvals || !dgx || !dgt || !dst || !dchk ||
-      (o->optimizer == MRBO_OPT_ADAM && (!dm || !dv)))
-    return fail(MRBO_ERR_NOMEM, "outer-ascent buffers");
-  if (!P->hchk && hipHostMalloc(&P->hchk, sizeof(int32_t) * 2 * mrbo_plan::NCHK) != hipSuccess) {
-    P->hchk = nullptr;
-    return fail(MRBO_ERR_NOMEM, "pinned check ring");
-  }
-  for (auto& e : P->chk_ev)
-    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(dx0, x0s, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync((void*)drn, rnstream, sizeof(double) * nrn, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync((void*)dxs, xstarts, sizeof(double) * nxs, hipMemcpyHostToDevice, st));
-    if (dual_y_dx) HIP_TRY(hipMemcpyAsync((void*)ddual, dual_y_dx, sizeof(double) * ndual, hipMemcpyHostToDevice, st));
-  }
-  // every restart starts active (stochastic_solve's loop runs until its eswavs break); Adam's
-  // moment estimates start at zero
-  hipLaunchKernelGGL(fill_int_kernel, dim3((R + 63) / 64), dim3(64), 0, st, (int*)dact, R, 1);
-  if (dm) {
-    HIP_TRY(hipMemsetAsync(dm, 0, sizeof(double) * nx, st));
-    HIP_TRY(hipMemsetAsync(dv, 0, sizeof(double) * nx, st));
-  }
-  // The iterations follow each other on the stream without a host round trip.  Behind them the
-  // host reads iteration j's check (status bits, restarts still active) LAG iterations later: once
-  // every restart has stopped, the launches already queued find x0 unchanged and reproduce the
-  // same trajectories and ETO rows bit for bit, so stopping a few iterations late changes no output.
-  constexpr int LAG = 2;
-  int it = 0, stopped_at = 0, bits = 0;
-  auto read_check = [&](int j) -> int {   // iteration j ≥ 1 (its slot not yet reused)
-    const int k = (j - 1) % mrbo_plan::NCHK;
-    if (hipEventSynchronize(P->chk_ev[k]) != hipSuccess) return -1;
-    bits |= P->hchk[2 * k];
-    if (P->hchk[2 * k + 1] == 0 && !stopped_at) stopped_at = j;
-    return 0;
-  };
-  // A restart that eswavs has stopped keeps its x0, so its trajectories would reproduce the
-  // outputs of its last launch bit for bit: the later launches skip them (kp.skip_active)
-  struct SkipGuard {
-    mrbo_plan_t* P;
-    ~SkipGuard() { P->skip_active = nullptr; }
-  } guard{P};
-  P->skip_active = dact;
-  // Without a caller's schedule (mrbo_plan_set_order), the launches after the first take their
-  // trajectories longest first by the first launch's work counters (mrbo_plan_order_longest_first:
-  // the launch's idle tail, C3 7.0 → 1.2 %); the plan's order is restored on return
-  struct OrderGuard {
-    mrbo_plan_t* P;
-    const int32_t* saved;
-    ~OrderGuard() { P->order = saved; }
-  } oguard{P, P->order};
-  // (a surrogate batch keeps the identity: the longest-first order is not defined across surrogates)
+  // a status bit ends the ascent; without a caller's schedule (mrbo_plan_set_order) the launches are
+  // ordered longest first (a surrogate batch keeps the identity: that order is not defined across surrogates)
   const bool auto_order = P->order == nullptr && o->iterations > 1 && P->S == 1;
-  int64_t* devals = auto_order ? (int64_t*)solve_slot(P, 13, sizeof(int64_t) * NCOUNT * T) : nullptr;
-  if (auto_order && !devals) return fail(MRBO_ERR_NOMEM, "outer-ascent work counters");
-  int rc = MRBO_OK;
-  while (it < o->iterations && !stopped_at && !bits) {
-    ++it;
-    rc = mrbo_simulate_mc(P, dx0, drn, dxs, ddual, nullptr, dvals, dgx, dgt, dst, nullptr, nullptr,
-                          (auto_order && it == 1) ? devals : nullptr, 0, st);
-    if (rc != MRBO_OK) return rc;
-    if (auto_order && it == 1) {
-      rc = mrbo_plan_order_longest_first(P, devals, nullptr, st);
-      if (rc != MRBO_OK) return rc;
-    }
-    rc = mrbo_eto_reduce(P, dvals, dgx, dgt, deto, 0, st);
-    if (rc != MRBO_OK) return rc;
-    if (o->optimizer == MRBO_OPT_SGA)
-      rc = mrbo_sga_step(P, deto, dx0, dact, sample_size, o->eta, 0, st);
-    else
-      rc = mrbo_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
-    if (rc != MRBO_OK) return rc;
-    const int k = (it - 1) % mrbo_plan::NCHK;
-    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)T, (const int*)dact, R,
-                       (int*)dchk + 2 * k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(P->hchk + 2 * k, dchk + 2 * k, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(P->chk_ev[k], st));
-    if (it > LAG && read_check(it - LAG)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
-  }
-  for (int j = std::max(1, it - LAG + 1); j <= it; ++j)   // the checks still in flight
-    if (read_check(j)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
+  Ascent a{P, st, host};
+  if (int rc = a.run(x0s, rnstream, xstarts, AscentOpts{o, dual_y_dx, true, auto_order, false, eto, active})) return rc;
   if (host) {
-    HIP_TRY(hipMemcpyAsync(x0s, dx0, sizeof(double) * nx, hipMemcpyDeviceToHost, st));
-    if (eto) HIP_TRY(hipMemcpyAsync(eto, deto, sizeof(double) * R * W, hipMemcpyDeviceToHost, st));
-    if (active) HIP_TRY(hipMemcpyAsync(active, dact, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
+    const size_t R = (size_t)P->p.R * P->S, W = 2 + 2 * P->d + 2;
+    HIP_TRY(hipMemcpyAsync(x0s, a.x0, sizeof(double) * a.nx, hipMemcpyDeviceToHost, st));
+    if (eto) HIP_TRY(hipMemcpyAsync(eto, a.eto, sizeof(double) * R * W, hipMemcpyDeviceToHost, st));
+    if (active) HIP_TRY(hipMemcpyAsync(active, a.act, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
-  result[0] = it;                              // iterations launched
-  result[1] = stopped_at ? stopped_at : it;    // the iteration after which no restart was active
-  result[2] = bits;                            // OR of every launch's trajectory status bits
+  if (int rc = a.read_trailing()) return rc;
+  result[0] = a.it;                                  // iterations launched
+  result[1] = a.stopped_at ? a.stopped_at : a.it;    // the iteration after which no restart was active
+  result[2] = a.bits;                                // OR of every launch's trajectory status bits
   return MRBO_OK;
 }
 
@@ -1331,9 +1407,6 @@ static int pick_common(mrbo_plan_t* P, const double* x, const double* eto, int i
   return MRBO_OK;
 }
 
-// slots of the plan's outer-ascent buffers (mrbo_plan::solve) that only the calls below use
-enum { SLOT_XNEXT = 14, SLOT_MEAN, SLOT_PICK, SLOT_MEANS, SLOT_NOVEL, SLOT_CV_BASE, SLOT_CV_VALUES, SLOT_CV_GRAD };
-
 int mrbo_pick_restart(mrbo_plan_t* P, const double* x, const double* eto, int32_t incumbent, double* xnext,
                       double* mean, int32_t* pick, double* means, uint32_t flags, void* stream) {
   if (!P || !x || !eto || !xnext || !mean || !pick) return fail(MRBO_ERR_ARG, "null argument");
@@ -1359,141 +1432,56 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   hipStream_t st = (hipStream_t)stream;
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
-  const bool moments = o->optimizer != MRBO_OPT_SGA;
-  const int d = P->d, M = P->p.M, R = P->p.R * P->S, S = P->S, h = P->p.h, W = 2 + 2 * d + 2;   // R·S restarts
-  const size_t T = (size_t)M * R;
-  const size_t nx = (size_t)d * R, nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
-  const double sample_size = o->sample_size > 0 ? o->sample_size : (double)M;
-  // device state, in mrbo_stochastic_solve's slots: x0, the inputs, the ETO rows, the stop flags, the
-  // launch outputs, the moments, the checks; then the pick's outputs
-  double* dx0 = host ? (double*)solve_slot(P, 0, sizeof(double) * nx) : x0s;
-  const double* drn = host ? (const double*)solve_slot(P, 1, sizeof(double) * nrn) : rnstream;
-  const double* dxs = host ? (const double*)solve_slot(P, 2, sizeof(double) * nxs) : xstarts;
-  double* deto = (double*)solve_slot(P, 4, sizeof(double) * R * W);
-  int32_t* dact = (host || !active) ? (int32_t*)solve_slot(P, 5, sizeof(int32_t) * R) : active;
-  double* dvals = (double*)solve_slot(P, 6, sizeof(double) * T);
-  double* dgx = (double*)solve_slot(P, 7, sizeof(double) * d * T);
-  double* dgt = (double*)solve_slot(P, 8, sizeof(double) * T);
-  // with the control variate (mrbo_plan_set_control_variate) every rollout launch is followed by its
-  // horizon-0 control launch: its status words stand behind the rollout's, so that one check reads both
-  const bool cv = P->control_variate != 0;
-  const size_t nst = cv ? 2 * T : T;
-  int32_t* dst = (int32_t*)solve_slot(P, 9, sizeof(int32_t) * nst);
-  double* dv0 = cv ? (double*)solve_slot(P, SLOT_CV_VALUES, sizeof(double) * T) : nullptr;
-  double* dg0 = cv ? (double*)solve_slot(P, SLOT_CV_GRAD, sizeof(double) * d * T) : nullptr;
-  if (cv && (!dv0 || !dg0)) return fail(MRBO_ERR_NOMEM, "control-variate buffers");
-  double* dm = moments ? (double*)solve_slot(P, 10, sizeof(double) * nx) : nullptr;
-  double* dv = moments ? (double*)solve_slot(P, 11, sizeof(double) * nx) : nullptr;
-  int32_t* dchk = (int32_t*)solve_slot(P, 12, sizeof(int32_t) * 2 * mrbo_plan::NCHK);
+  const int d = P->d, S = P->S;
+  const size_t R = (size_t)P->p.R * S;
+  // the outputs of the pick; the rest of the device state is the ascent's
   double* dxn = host ? (double*)solve_slot(P, SLOT_XNEXT, sizeof(double) * d * S) : xnext;
   double* dmean = host ? (double*)solve_slot(P, SLOT_MEAN, sizeof(double) * S) : mean;
   int32_t* dpick = host ? (int32_t*)solve_slot(P, SLOT_PICK, sizeof(int32_t) * S) : pick;
   double* dmeans = (host || !means) ? (double*)solve_slot(P, SLOT_MEANS, sizeof(double) * R) : means;
   int* dnovel = (int*)solve_slot(P, SLOT_NOVEL, sizeof(int) * R);
-  if (!dx0 || !drn || !dxs || !deto || !dact || !dvals || !dgx || !dgt || !dst || !dchk || !dxn || !dmean || !dpick ||
-      !dmeans || !dnovel || (moments && (!dm || !dv)))
-    return fail(MRBO_ERR_NOMEM, "acquisition-solve buffers");
-  if (!P->hchk && hipHostMalloc(&P->hchk, sizeof(int32_t) * 2 * mrbo_plan::NCHK) != hipSuccess) {
-    P->hchk = nullptr;
-    return fail(MRBO_ERR_NOMEM, "pinned check ring");
-  }
-  for (auto& e : P->chk_ev)
-    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(dx0, x0s, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync((void*)drn, rnstream, sizeof(double) * nrn, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync((void*)dxs, xstarts, sizeof(double) * nxs, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(fill_int_kernel, dim3((R + 63) / 64), dim3(64), 0, st, (int*)dact, R, 1);
-  if (moments) {
-    HIP_TRY(hipMemsetAsync(dm, 0, sizeof(double) * nx, st));
-    HIP_TRY(hipMemsetAsync(dv, 0, sizeof(double) * nx, st));
-  }
-  // The ascent, as mrbo_stochastic_solve runs it: iteration j's check (status bits, restarts still
-  // active) is read LAG iterations behind the launches, and a stopped restart is skipped by the
-  // later launches (kp.skip_active) -- its outputs and ETO row stay those of its last launch, which
-  // the host loop's relaunch reproduces bit for bit.  Status bits are collected, not acted on.
-  constexpr int LAG = 2;
-  int it = 0, stopped_at = 0, bits = 0;
-  auto read_check = [&](int j) -> int {   // iteration j ≥ 1 (its slot not yet reused)
-    const int k = (j - 1) % mrbo_plan::NCHK;
-    if (hipEventSynchronize(P->chk_ev[k]) != hipSuccess) return -1;
-    bits |= P->hchk[2 * k];
-    if (P->hchk[2 * k + 1] == 0 && !stopped_at) stopped_at = j;
-    return 0;
-  };
-  struct SkipGuard {
-    mrbo_plan_t* P;
-    ~SkipGuard() { P->skip_active = nullptr; }
-  } guard{P};
-  P->skip_active = dact;
-  int rc = MRBO_OK;
-  while (it < o->iterations && !stopped_at) {
-    ++it;
-    rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, dgx, dgt, dst, nullptr, nullptr, nullptr, 0, st);
-    if (rc != MRBO_OK) return rc;
-    if (cv) {   // the control launch skips the stopped restarts too; their rows keep their bits
-      rc = mrbo_simulate_control(P, dx0, drn, dxs, dv0, dg0, dst + T, 0, st);
-      if (rc != MRBO_OK) return rc;
-      rc = mrbo_eto_reduce_cv(P, dx0, dvals, dgx, dgt, dv0, dg0, deto, nullptr, 0, st);
-    } else {
-      rc = mrbo_eto_reduce(P, dvals, dgx, dgt, deto, 0, st);
-    }
-    if (rc != MRBO_OK) return rc;
-    if (o->optimizer == MRBO_OPT_SGA)
-      rc = mrbo_sga_step(P, deto, dx0, dact, sample_size, o->eta, 0, st);
-    else if (o->optimizer == MRBO_OPT_ADAM)
-      rc = mrbo_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
-    else
-      rc = mrbo_box_adam_step(P, deto, dx0, dact, dm, dv, it, sample_size, o->eta, o->beta1, o->beta2, o->eps, 0, st);
-    if (rc != MRBO_OK) return rc;
-    const int k = (it - 1) % mrbo_plan::NCHK;
-    hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)nst, (const int*)dact,
-                       R, (int*)dchk + 2 * k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(P->hchk + 2 * k, dchk + 2 * k, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(P->chk_ev[k], st));
-    if (it > LAG && read_check(it - LAG)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
-  }
+  if (!dxn || !dmean || !dpick || !dmeans || !dnovel) return fail(MRBO_ERR_NOMEM, "acquisition-solve buffers");
+  // The ascent: status bits are collected, not acted on; with the control variate
+  // (mrbo_plan_set_control_variate) its rows are mrbo_eto_reduce_cv's
+  const bool cv = P->control_variate != 0;
+  const mrbo_solve_opts_t step{o->optimizer, o->iterations, o->eta, o->beta1, o->beta2, o->eps, o->sample_size};
+  Ascent a{P, st, host};
+  int rc = a.run(x0s, rnstream, xstarts, AscentOpts{&step, nullptr, false, false, cv, nullptr, active});
+  if (rc != MRBO_OK) return rc;
   // rollout_solve's tail: the end points projected onto the box, one launch without gradients at
   // them with nothing skipped, the ETO means, the pick.  Its check goes to the ring slot after the
   // last iteration's: read long ago, and not one of the (at most LAG) checks still in flight.
-  P->skip_active = nullptr;
-  launch_box_project(st, dx0, (long long)nx, d, P->dlbs, P->dubs);
+  launch_box_project(st, a.x0, (long long)a.nx, d, P->dlbs, P->dubs);
   HIP_TRY(hipGetLastError());
-  rc = mrbo_simulate_mc(P, dx0, drn, dxs, nullptr, nullptr, dvals, nullptr, nullptr, dst, nullptr, nullptr, nullptr,
-                        MRBO_FLAG_NO_GRADIENT, st);
+  rc = mrbo_simulate_mc(P, a.x0, a.rn, a.xs, nullptr, nullptr, a.vals, nullptr, nullptr, a.status, nullptr, nullptr,
+                        nullptr, MRBO_FLAG_NO_GRADIENT, st);
   if (rc != MRBO_OK) return rc;
   if (cv) {   // the means the pick ranks are the control-variate ones as well
-    rc = mrbo_simulate_control(P, dx0, drn, dxs, dv0, nullptr, dst + T, MRBO_FLAG_NO_GRADIENT, st);
+    rc = mrbo_simulate_control(P, a.x0, a.rn, a.xs, a.v0, nullptr, a.status + a.T, MRBO_FLAG_NO_GRADIENT, st);
     if (rc != MRBO_OK) return rc;
-    rc = mrbo_eto_reduce_cv(P, dx0, dvals, nullptr, nullptr, dv0, nullptr, deto, nullptr, 0, st);
+    rc = mrbo_eto_reduce_cv(P, a.x0, a.vals, nullptr, nullptr, a.v0, nullptr, a.eto, nullptr, 0, st);
   } else {
-    rc = mrbo_eto_reduce(P, dvals, nullptr, nullptr, deto, 0, st);
+    rc = mrbo_eto_reduce(P, a.vals, nullptr, nullptr, a.eto, 0, st);
   }
   if (rc != MRBO_OK) return rc;
-  rc = pick_common(P, dx0, deto, o->incumbent, dxn, dmean, dpick, dmeans, dnovel, st);
+  rc = pick_common(P, a.x0, a.eto, o->incumbent, dxn, dmean, dpick, dmeans, dnovel, st);
   if (rc != MRBO_OK) return rc;
-  const int kf = it % mrbo_plan::NCHK;
-  hipLaunchKernelGGL(solve_check_kernel, dim3(1), dim3(256), 0, st, (const int*)dst, (long long)nst, (const int*)dact, R,
-                     (int*)dchk + 2 * kf);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(P->hchk + 2 * kf, dchk + 2 * kf, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+  const int kf = a.it % mrbo_plan::NCHK;
+  if ((rc = a.post_check(kf)) != MRBO_OK) return rc;
   if (host) {
-    HIP_TRY(hipMemcpyAsync(x0s, dx0, sizeof(double) * nx, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(x0s, a.x0, sizeof(double) * a.nx, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(xnext, dxn, sizeof(double) * d * S, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(mean, dmean, sizeof(double) * S, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(pick, dpick, sizeof(int32_t) * S, hipMemcpyDeviceToHost, st));
     if (means) HIP_TRY(hipMemcpyAsync(means, dmeans, sizeof(double) * R, hipMemcpyDeviceToHost, st));
-    if (active) HIP_TRY(hipMemcpyAsync(active, dact, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
+    if (active) HIP_TRY(hipMemcpyAsync(active, a.act, sizeof(int32_t) * R, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));   // the call's one synchronisation (the lagged reads aside)
-  for (int j = std::max(1, it - LAG + 1); j <= it; ++j)   // the last checks: complete by now
-    if (read_check(j)) return fail(MRBO_ERR_HIP, "hipEventSynchronize");
-  result[0] = it;                              // iterations launched
-  result[1] = stopped_at ? stopped_at : it;    // the iteration after which no restart was active
-  result[2] = bits;                            // OR of the status bits of the ascent's launches
-  result[3] = P->hchk[2 * kf];                 // ... of the final launch
+  if ((rc = a.read_trailing()) != MRBO_OK) return rc;   // the last checks: complete by now
+  result[0] = a.it;                                  // iterations launched
+  result[1] = a.stopped_at ? a.stopped_at : a.it;    // the iteration after which no restart was active
+  result[2] = a.bits;                                // OR of the status bits of the ascent's launches
+  result[3] = P->hchk[2 * kf];                       // ... of the final launch
   return MRBO_OK;
 }
 

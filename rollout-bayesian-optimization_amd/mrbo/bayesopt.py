@@ -32,11 +32,10 @@ from . import testfns as T
 from .decision_rules import EI, LCB, POI
 from .kernels import Matern52
 from .optimizers import Adam, StandardSGA
-from .rollout import _plan_for, _plan_for_multi, simulate_trajectory_mc_batch, simulate_trajectory_mc_multi
+from .rollout import _plan_for_multi, simulate_trajectory_mc_multi
 from .surrogates import FantasySurrogate, Surrogate
 from .trajectory import Trajectory, TrajectoryParameters
-from .utils import (ExperimentSetup, gap, generate_batch, simple_regret, stochastic_solve_batch,
-                    stochastic_solve_multi)
+from .utils import ExperimentSetup, gap, generate_batch, simple_regret, stochastic_solve_multi
 
 INITIAL_OBSERVATIONS = 5            # nonmyopic_bayesopt.jl:131
 METRICS = ["times", "gaps", "allocations", "simple_regret", "minimum_observations"]   # :191
@@ -150,33 +149,21 @@ def rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_it
     (mrbo_rollout_solve) with the same results; the default keeps the host-driven loop.
     variance_reduction=True (the reference's --variance-reduction): every ETO row of the ascent and
     the final means use EI0 at the restart's point as a control variate (mrbo/variance.py, DESIGN.md
-    §16), on either path with the same results."""
-    lbs, ubs = np.asarray(lbs, float), np.asarray(ubs, float)
-    batch = generate_batch(batch_size, lbs, ubs)
-    if incumbent:
-        batch = np.hstack([batch, incumbent_start(sur, lbs, ubs)[:, None]])
-    tp = TrajectoryParameters(start=batch[:, 0], hypers=[theta], horizon=horizon, mc_iterations=mc_samples,
-                              use_low_discrepancy_sequence=True, spatial_lowerbounds=lbs, spatial_upperbounds=ubs)
-    es = ExperimentSetup(tp, number_of_starts=starts)
-    traj = Trajectory(sur, FantasySurrogate(sur, horizon), start=batch[:, 0], hypers=[theta], horizon=horizon)
-    if device_solve:
-        plan = _plan_for(sur, horizon, tp.rnstream_sequence.shape[0], batch.shape[1], es.get_starts().shape[1], lbs,
-                         ubs, traj.θ[0], device, {})
-        r = _device_solve(plan, batch, tp, es, sgd_iterations, eta, solver, incumbent, variance_reduction)
-        if trace is not None:
-            trace.append(dict(batch=batch, x=r["x"], means=r["means"][:, 0], pick=int(r["pick"][0]),
-                              result=r["result"]))
-        return r["xnext"][:, 0].copy(), float(r["mean"][0])
-    opts = [StandardSGA(η=eta) if solver == "sga" else BoxAdam(lbs, ubs, η=eta) for _ in range(batch.shape[1])]
-    x, history = stochastic_solve_batch(opts, sur, tp, es, batch, T=traj, iterations=sgd_iterations, device=device,
-                                        variance_reduction=variance_reduction)
-    x = np.clip(x, lbs[:, None], ubs[:, None])
-    etos = simulate_trajectory_mc_batch(traj, tp, x, es.get_starts(), with_gradient=False, device=device,
-                                        variance_reduction=variance_reduction).etos(with_gradient=False)
-    k, means = pick_restart(sur, x, etos, lbs, ubs, incumbent)
+    §16), on either path with the same results.
+    rollout_solve_multi on the one surrogate; the trace entry drops the surrogate axis."""
+    multi = None if trace is None else []
+    (out,) = rollout_solve_multi([sur], lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta,
+                                 eta=eta, device=device, solver=solver, incumbent=incumbent, trace=multi,
+                                 device_solve=device_solve, variance_reduction=variance_reduction)
     if trace is not None:
-        trace.append(dict(batch=batch, x=x.copy(), means=means, pick=k, history=history))
-    return x[:, k].copy(), float(means[k])
+        t = multi[0]
+        entry = dict(batch=t["batch"][:, :, 0], x=t["x"][:, :, 0], means=t["means"][:, 0], pick=t["pick"][0])
+        if device_solve:
+            entry["result"] = t["result"]
+        else:
+            entry["history"] = [etos[0] for etos in t["history"]]
+        trace.append(entry)
+    return out
 
 
 def pick_restart(sur, x, etos, lbs, ubs, incumbent):

@@ -44,18 +44,8 @@ class RolloutPlan:
 
     def __init__(self, X, L, c, y, kernel, lengthscale, sigma_n2, fmini, h, M, R, nstarts, lbs, ubs, theta,
                  device=0, period=1.0, **opts):
-        self.lib = _lib.load()
-        self.S = 1
-        self._X, self._L, self._c, self._y = _f64(X), _f64(L), _f64(c), _f64(y)
-        self.d, self.N = self._X.shape
-        dp = ctypes.POINTER(ctypes.c_double)
-        sd = _lib.SurrogateDesc(self.d, self.N, int(kernel), float(lengthscale), float(sigma_n2), float(fmini),
-                                self._X.ctypes.data_as(dp), self._L.ctypes.data_as(dp), self.N,
-                                self._c.ctypes.data_as(dp), self._y.ctypes.data_as(dp), float(period))
-        pd = self._params(h, M, R, nstarts, lbs, ubs, theta, device, opts)
-        h_ = ctypes.c_void_p()
-        _lib.check(self.lib.mrbo_plan_create(ctypes.byref(sd), ctypes.byref(pd), int(device), ctypes.byref(h_)))
-        self.handle = h_
+        self._create([dict(X=X, L=L, c=c, y=y, kernel=kernel, lengthscale=lengthscale, sigma_n2=sigma_n2,
+                           fmini=fmini, period=period)], h, M, R, nstarts, lbs, ubs, theta, device, opts)
 
     @classmethod
     def from_surrogates(cls, surrogates, h, M, R, nstarts, lbs, ubs, theta, device=0, **opts):
@@ -65,8 +55,6 @@ class RolloutPlan:
         sigma_n2; R is the number of restarts PER surrogate, and everything else is shared.  Inputs
         and outputs carry the surrogate index slowest (x0s d×R×S, values M×R×S, ...); block q of every
         output is bit-identical to a plain plan on surrogate q."""
-        self = cls.__new__(cls)
-        self.lib = _lib.load()
         surrogates = list(surrogates)
         if not surrogates:
             raise ValueError("from_surrogates needs at least one surrogate")
@@ -74,6 +62,13 @@ class RolloutPlan:
             missing = [k for k in SURROGATE_KEYS if k not in s]
             if missing:
                 raise ValueError(f"surrogate {q} lacks {missing}")
+        self = cls.__new__(cls)
+        self._create(surrogates, h, M, R, nstarts, lbs, ubs, theta, device, opts)
+        return self
+
+    def _create(self, surrogates, h, M, R, nstarts, lbs, ubs, theta, device, opts):
+        """The plan of the surrogate mappings `surrogates` (a plain plan: one), mrbo_plan_create_batch."""
+        self.lib = _lib.load()
         self.S = len(surrogates)
         dp = ctypes.POINTER(ctypes.c_double)
         self._keep = []     # the host arrays the descriptors point into, alive until the create returns
@@ -93,7 +88,6 @@ class RolloutPlan:
         h_ = ctypes.c_void_p()
         _lib.check(self.lib.mrbo_plan_create_batch(sds, self.S, ctypes.byref(pd), int(device), ctypes.byref(h_)))
         self.handle = h_
-        return self
 
     def _params(self, h, M, R, nstarts, lbs, ubs, theta, device, opts):
         """mrbo_params_t of the plan (and the plan's own copies of the sizes)."""

@@ -31,21 +31,8 @@ def _state_key(s):
 
 
 def _plan_for(s, h, M, R, nstarts, lbs, ubs, theta, device, opts):
-    g = s.get_decision_rule()
-    opts = dict(opts)
-    opts.setdefault("rule", g.rule_id)       # the surrogate's base decision rule (Q12: T.θ)
-    opts.setdefault("sigma_tol", g.σtol)
-    key = (_state_key(s), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()), tuple(np.asarray(ubs).ravel()),
-           float(theta), device, tuple(sorted(opts.items())))
-    p = _PLANS.get(key)
-    if p is None:
-        n = s.observed
-        p = RolloutPlan(s.X[:, :n], s.L[:n, :n], s.c[:n], s.y[:n], s.ψ.kind, s.ψ.lengthscale, s.σn2, s.fmini(),
-                        h, M, R, nstarts, lbs, ubs, theta, device=device, period=s.ψ.period, **opts)
-        if len(_PLANS) > 16:
-            _PLANS.clear()
-        _PLANS[key] = p
-    return p
+    """The cached plan of one surrogate: the S = 1 surrogate batch."""
+    return _plan_for_multi([s], h, M, R, nstarts, lbs, ubs, theta, device, opts)
 
 
 def surrogate_dict(s):
@@ -76,12 +63,12 @@ def check_surrogate_batch(surrogates):
 
 
 def _plan_for_multi(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts):
-    """_plan_for for a surrogate batch: one RolloutPlan.from_surrogates plan, cached on the
-    surrogates' identities, versions and contents (_state_key)."""
+    """The plan cache: one RolloutPlan.from_surrogates plan for the surrogates `ss`, cached on their
+    identities, versions and contents (_state_key)."""
     check_surrogate_batch(ss)
     g = ss[0].get_decision_rule()
     opts = dict(opts)
-    opts.setdefault("rule", g.rule_id)
+    opts.setdefault("rule", g.rule_id)       # the surrogates' base decision rule (Q12: T.θ)
     opts.setdefault("sigma_tol", g.σtol)
     key = (tuple(_state_key(s) for s in ss), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()),
            tuple(np.asarray(ubs).ravel()), float(theta), device, tuple(sorted(opts.items())))
@@ -141,25 +128,14 @@ def simulate_trajectory_mc_batch(T, tp, x0s, inner_solve_xstarts, with_gradient=
     """R restarts (columns of x0s) × tp.mc_iters samples in one kernel launch.  variance_reduction=True:
     a second launch at horizon 0 follows and the ETO rows are the control-variate ones
     (RolloutPlan.simulate_control / eto_cv); the per-trajectory outputs are unchanged."""
-    import torch
     x0s = np.asarray(x0s, dtype=np.float64)
     if x0s.ndim == 1:
         x0s = x0s.reshape(-1, 1)
-    d, R = x0s.shape
-    lbs, ubs = tp.get_spatial_bounds()
-    rn = tp.rnstream_sequence if rnstream is None else rnstream
-    M = rn.shape[0]
-    plan = _plan_for(T.s, tp.horizon, M, R, inner_solve_xstarts.shape[1], lbs, ubs, T.θ[0], device, opts)
-    dev = f"cuda:{device}"
-    dx0 = to_device(x0s, dev)
-    drn = rn if isinstance(rn, torch.Tensor) else to_device(rn, dev)
-    dxs = to_device(inner_solve_xstarts, dev)
-    ddy = None if dual_y_dx is None else to_device(dual_y_dx, dev)
-    drp = None if replay_x is None else to_device(replay_x, dev)
-    out = plan.alloc_outputs(with_gradient=with_gradient, want_policy=want_policy, want_obs=want_obs)
-    plan.simulate(dx0, drn, dxs, out, dual_y_dx=ddy, replay_x=drp)
-    eto = _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction)
-    return BatchResult(plan, out, eto)
+    last = lambda a: None if a is None else np.asarray(a)[..., None]   # the S axis of the one surrogate
+    return simulate_trajectory_mc_multi([T], tp, last(x0s), inner_solve_xstarts, with_gradient=with_gradient,
+                                        dual_y_dx=last(dual_y_dx), replay_x=last(replay_x), want_policy=want_policy,
+                                        want_obs=want_obs, device=device, rnstream=rnstream,
+                                        variance_reduction=variance_reduction, **opts)[0]
 
 
 def _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction):
@@ -169,13 +145,6 @@ def _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction):
         return plan.eto(out)
     ctl = plan.simulate_control(dx0, drn, dxs, with_gradient=with_gradient)
     return plan.eto_cv(dx0, out, ctl, want_beta=False)[0]
-
-
-class _PlanView:
-    """The sizes BatchResult reads, for one surrogate's block of a surrogate-batch launch."""
-
-    def __init__(self, plan):
-        self.d, self.M, self.R, self.h = plan.d, plan.M, plan.R, plan.h
 
 
 def check_multi_x0s(x0s, S, d=None):
@@ -225,12 +194,11 @@ def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient
                   dual_y_dx=None if dual_y_dx is None else to_device(dual_y_dx, dev),
                   replay_x=None if replay_x is None else to_device(replay_x, dev))
     eto = _eto(plan, dx0, drn, dxs, out, with_gradient, variance_reduction)   # variance_reduction: as the batch call
-    view = _PlanView(plan)
     W = 2 + 2 * d + 2
     res = []
     for q in range(S):   # block q of every flat output: the surrogate index is the slowest
         oq = {k: v[q * (v.numel() // S):(q + 1) * (v.numel() // S)] for k, v in out.items()}
-        res.append(BatchResult(view, oq, eto[q * W * R:(q + 1) * W * R]))
+        res.append(BatchResult(plan, oq, eto[q * W * R:(q + 1) * W * R]))   # plan.R: restarts per surrogate
     return res
 
 

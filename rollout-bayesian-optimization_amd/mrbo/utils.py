@@ -192,30 +192,12 @@ def stochastic_solve_batch(optimizers, surrogate, tp, es, starts, T=None, iterat
                            variance_reduction=False, **opts):
     """R restarts of the outer ascent at once: one batched rollout launch per SGA iteration;
     each restart keeps its own optimizer state and eswavs stop flag.  variance_reduction=True: every
-    iteration's ETO rows are the control-variate ones (a second launch at horizon 0)."""
-    from .rollout import simulate_trajectory_mc_batch
-    from .surrogates import FantasySurrogate
-    from .trajectory import Trajectory
-    x = np.array(starts, dtype=np.float64)
-    d, R = x.shape
-    if T is None:
-        T = Trajectory(surrogate, FantasySurrogate(surrogate, tp.horizon), start=x[:, 0], hypers=tp.θ,
-                       horizon=tp.horizon)
-    active = np.ones(R, dtype=bool)
-    history = []
-    for _ in range(iterations):
-        if not active.any():
-            break
-        br = simulate_trajectory_mc_batch(T, tp, x, es.get_starts(), device=device,
-                                          variance_reduction=variance_reduction, **opts)
-        etos = br.etos()
-        history.append(etos)
-        for r in range(R):
-            if not active[r]:
-                continue
-            e = etos[r]
-            if eswavs(e.gradient(), e.std_gradient() ** 2, tp.mc_iters):
-                active[r] = False
-                continue
-            optimizers[r].update(x[:, r], e.gradient())
-    return x, history
+    iteration's ETO rows are the control-variate ones (a second launch at horizon 0).
+    stochastic_solve_multi on the one surrogate; returns (x d×R, history: per iteration the R ETOs)."""
+    starts = np.asarray(starts, dtype=np.float64)
+    if starts.ndim != 2:
+        raise ValueError(f"starts must be d×R; got {starts.shape}")
+    x, history = stochastic_solve_multi([optimizers], [surrogate], tp, es, starts[:, :, None],
+                                        Ts=None if T is None else [T], iterations=iterations, device=device,
+                                        variance_reduction=variance_reduction, **opts)
+    return x[:, :, 0], [etos[0] for etos in history]
