@@ -608,6 +608,12 @@ __device__ __forceinline__ Exp2 xexp2(double a, double b) {
   r.b = fexp(b);
   return r;
 }
+// ONE_PLUS_S_FUSED: 1 + s of both g1 is written as fma(c, √ρ², 1), one rounding.  The plain form
+// leaves that contraction to the compiler, which decides it per inlined copy and per row: in the
+// Newton sites of the benchmarked kernel it had contracted both rows, and the evaluation sites with
+// a compile-time mode (evaluate<…, MODE>) ask for exactly that, so their g1 keeps its bits whatever
+// the code around them becomes.
+template <bool ONE_PLUS_S_FUSED = false>
 __device__ __forceinline__ void rad_eval2(const Radial& k, double rho2a, double rho2b, double& psia, double& g1a,
                                           double& g2a, double& psib, double& g1b, double& g2b) {
   if (k.kind != 0) {
@@ -616,13 +622,16 @@ __device__ __forceinline__ void rad_eval2(const Radial& k, double rho2a, double 
     return;
   }
   const double c = k.cK, c23 = c * c * (1.0 / 3.0);
-  const double sa = c * fast_sqrt0(rho2a), sb = c * fast_sqrt0(rho2b);
+  const double ra = fast_sqrt0(rho2a), rb = fast_sqrt0(rho2b);
+  const double sa = c * ra, sb = c * rb;
   const Exp2 e = xexp2(-sa, -sb);
   psia = fma(sa, fma(sa, 1.0 / 3.0, 1.0), 1.0) * e.a;
-  g1a = -c23 * (1.0 + sa) * e.a;
+  if constexpr (ONE_PLUS_S_FUSED) g1a = -c23 * fma(c, ra, 1.0) * e.a;
+  else g1a = -c23 * (1.0 + sa) * e.a;
   g2a = c23 * (c * c) * e.a;
   psib = fma(sb, fma(sb, 1.0 / 3.0, 1.0), 1.0) * e.b;
-  g1b = -c23 * (1.0 + sb) * e.b;
+  if constexpr (ONE_PLUS_S_FUSED) g1b = -c23 * fma(c, rb, 1.0) * e.b;
+  else g1b = -c23 * (1.0 + sb) * e.b;
   g2b = c23 * (c * c) * e.b;
 }
 

@@ -582,6 +582,9 @@ enum { NT_STOP = 0,        // the iteration ends here
 template <int D, int RPL, int HW>
 __device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, NewtonState& ns);
 
+// evaluate<…, MODE = EV_RT>: the mode is not a template argument but the run-time argument
+constexpr int EV_RT = -1;
+
 // ================================================================================
 // eval(fs, x, θ; fantasy_index = S)  -- radial_basis_surrogates.jl:482-581
 //   x is read from U[U_X].  Results land in U (lane-uniform) and `lr` (per lane).
@@ -593,14 +596,21 @@ __device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const 
 // decision code (newton_after_value) runs here, right after the σ / EI part, and leaves its outcome
 // in nt->why.  With kp.newton_fused, an outcome NT_CONTINUE does not return: the call goes on with
 // the GRADC evaluation at the same x that the caller would issue next, the projected-gradient test
-// and the BACK part (back_after) -- the same code, instantiated once more with INNER -- and returns
-// EVR_GRAD as well.
-template <int D, int RPL, int HW, bool INNER = false>
-__device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int mode, LaneRes<D, RPL, HW>& lr,
-                                        int kst = 0, bool back_after = false, NewtonState* nt = nullptr) {
+// and the BACK part (back_after) -- the same code, instantiated once more with MODE = EV_GRADC --
+// and returns EVR_GRAD as well.
+// MODE: the mode as a template argument (the Newton sites of the square full-wave layout), or EV_RT:
+// the mode is the run-time argument mode_rt.  With a fixed MODE, `mode` below and everything derived
+// from it (all_cols, do_val, rows_kept, the product arm, the reductions that run, the exits) are
+// constant expressions: the arms of other modes are never emitted, whatever the inliner does.
+template <int D, int RPL, int HW, int MODE = EV_RT>
+__device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int mode_rt,
+                                        LaneRes<D, RPL, HW>& lr, int kst = 0, bool back_after = false,
+                                        NewtonState* nt = nullptr) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1, BS = Ly::BS, NR = Ly::NR;
   constexpr bool FUSABLE = Ly::SQ && HW == 1;
+  static_assert(MODE == EV_RT || (MODE >= EV_VALUE && MODE <= EV_GSTART), "evaluate: MODE");
+  const int mode = MODE == EV_RT ? mode_rt : MODE;   // a constant expression when MODE is fixed
   // Opaque copy of the lane index: keeps the per-lane LDS/global addresses derived from it
   // inside this evaluation instead of being hoisted (and held live in VGPRs) across the
   // caller's Newton / horizon loops -- the difference between 1 and 3-4 waves per SIMD.
@@ -659,7 +669,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       double rho2f = 0.0;
 #pragma unroll
       for (int a = 0; a < D; ++a) { rf[a] = x[a] - U[Ly::U_XF + fl * D + a]; rho2f = fma(rf[a], rf[a], rho2f); }
-      rad_eval2(W.rad, rho2, rho2f, psi, g1, g2, psif, g1f, g2f);
+      rad_eval2<MODE != EV_RT>(W.rad, rho2, rho2f, psi, g1, g2, psif, g1f, g2f);
     } else {
       rad_eval(W.rad, rho2, psi, g1, g2);
     }
@@ -998,7 +1008,8 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
         // the iteration continues at this x: GRADC, the projected-gradient test and BACK here, in
         // an instantiation of their own (mode is a compile-time constant in it, and a backward
         // branch into the code above would make this body a loop, whose hoisted invariants spill)
-        if constexpr (!INNER) return EVR_GRAD | evaluate<D, RPL, HW, true>(W, kp, S, EV_GRADC, lr, kst, true);
+        if constexpr (MODE != EV_GRADC)
+          return EVR_GRAD | evaluate<D, RPL, HW, EV_GRADC>(W, kp, S, EV_GRADC, lr, kst, true);
       }
     }
     return 0;
@@ -1689,7 +1700,8 @@ __device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const 
 }
 
 // Deterministic projected Newton on f = -α over the box, from start k.
-// A state machine around ONE evaluate() call site.  Work is lazy, decisions are not: every
+// Square full-wave layout: straight-line around evaluation sites whose mode is a template argument;
+// the other layouts: a state machine around one site with a run-time mode.  Work is lazy, decisions are not: every
 // point gets a value-only evaluation; the gradient columns are completed (GRADC) only where
 // the certificate cannot rule out a step, the backward product and Hα (BACK) only where a
 // step is taken.  Values and gradients are bit-identical to a FULL evaluation at the same
@@ -1719,7 +1731,6 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   // stop the iteration, so it begins with the gradient at x_start
   // (GSTART takes the base forward product from the square layout's per-workgroup tables; the
   // packed layouts evaluate the gradient at the start point in full)
-  int phase = have_f0 ? P_GRAD : P_VAL, mode = have_f0 ? (Ly::SQ ? EV_GSTART : EV_GRAD) : EV_VALUE;
   // square full-wave layout: the decision code after a VALUE evaluation runs inside the evaluation
   // call, which with kp.newton_fused goes on to GRADC + BACK where the iteration continues
   constexpr bool FUSABLE = Ly::SQ && HW == 1;
@@ -1732,26 +1743,66 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   ns.ls = 0;
   ns.st = 0;
   ns.why = NT_STOP;
+  if constexpr (FUSABLE) {
+    // Every evaluation site has its mode as a template argument (evaluate<…, MODE>): the head of
+    // the run, then per iteration direction -> trial point -> VALUE, straight-line.
+    int ran;
+    bool gradc;   // the gradient columns at x are still to run (the two-call loop, kp.newton_fused off)
+    bool run = true;
+    if (have_f0) {   // head of a batched run: GSTART + projected-gradient test + BACK
+      ran = evaluate<D, RPL, HW, EV_GSTART>(W, kp, S, EV_GSTART, lr, k, true);
+      gradc = false;
+    } else {         // head of a run without a batched start value: VALUE at the start point
+      ns.trial = false;
+      ran = evaluate<D, RPL, HW, EV_VALUE>(W, kp, S, EV_VALUE, lr, k, false, &ns);
+      ++nevals.value;
+      run = (ns.why != NT_STOP);
+      gradc = !(ran & EVR_GRAD);
+    }
+    while (run) {
+      // the two-call loop: GRADC + projected-gradient test + BACK at x in a call of their own
+      if (gradc) ran = evaluate<D, RPL, HW, EV_GRADC>(W, kp, S, EV_GRADC, lr, k, true);
+      ++nevals.grad;
+      if (!(ran & EVR_BACK)) break;       // the projected-gradient test inside the evaluation: stationary
+      ++nevals.hess;                      // the BACK part (Hα) ran in the same call: step
+      STAMP(W, 12);
+      const bool go = newton_direction<D, RPL, HW>(W, kp);
+      STAMP(W, 13);
+      if (!go) break;
+      ns.t = 1.0;
+      ns.ls = 0;
+      ns.trial = true;
+      do {   // a backtrack repeats only the trial point and the VALUE call
+        ns.dec = newton_trial_point<D, RPL, HW>(W, ns.t);
+        STAMP(W, 14);
+        ran = evaluate<D, RPL, HW, EV_VALUE>(W, kp, S, EV_VALUE, lr, k, false, &ns);
+        ++nevals.value;
+      } while (ns.why == NT_BACKTRACK);
+      if (ns.why == NT_STOP) break;
+      gradc = !(ran & EVR_GRAD);          // fused: the columns, the test and BACK ran in the trial's call
+    }
+  } else {
+  // A state machine around one evaluate() call site with a run-time mode.
+  // have_f0: (the packed layouts evaluate the gradient at the start point in full; the half-wave
+  // kernel takes GSTART's base forward product from the per-workgroup tables as above)
+  int phase = have_f0 ? P_GRAD : P_VAL, mode = have_f0 ? (Ly::SQ ? EV_GSTART : EV_GRAD) : EV_VALUE;
   for (;;) {
     ns.trial = (phase == P_TRIAL);
     // P_GRAD: GRAD + BACK in one evaluation call (evaluate back_after)
-    const int ran = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, phase == P_GRAD, FUSABLE ? &ns : nullptr);
+    const int ran = evaluate<D, RPL, HW>(W, kp, S, mode, lr, k, phase == P_GRAD);
     if (mode == EV_VALUE) ++nevals.value;
     else if (mode == EV_GRADC || mode == EV_GRAD || mode == EV_GSTART) ++nevals.grad;
     else ++nevals.hess;
     if (mode == EV_VALUE) {   // the start point (P_VAL) or a line-search trial (P_TRIAL)
-      if constexpr (!FUSABLE) ns.why = newton_after_value<D, RPL, HW>(W, kp, S, ns);
+      ns.why = newton_after_value<D, RPL, HW>(W, kp, S, ns);
       if (ns.why == NT_STOP) break;
       if (ns.why == NT_BACKTRACK) {
         ns.dec = newton_trial_point<D, RPL, HW>(W, ns.t);
         continue;
       }
       phase = P_GRAD;
-      if (!(ran & EVR_GRAD)) {   // the two-call loop: the gradient columns at x in a call of their own
-        mode = EV_GRADC;
-        continue;
-      }
-      ++nevals.grad;             // they ran in the same call, with the projected-gradient test
+      mode = EV_GRADC;        // the gradient columns at x in a call of their own
+      continue;
     }
     if (phase == P_GRAD) {   // the projected-gradient test ran inside the evaluation
       if (!(ran & EVR_BACK)) break;       // stationary
@@ -1771,6 +1822,7 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
       mode = EV_VALUE;
       continue;
     }
+  }
   }
   st |= ns.st;
   wave_sync();
