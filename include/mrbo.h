@@ -193,6 +193,21 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* s, int32_t S, const mrbo_para
  *              Hessian completions, adjoint rich evals, adjoint perturbation pairs] -- the work
  *              counters of the FLOP roofline model (inner-solve counts are identical to the
  *              oracle's: same lazy Newton iteration)
+ * Failed trajectories (status != 0; tests/test_gpu_failure_paths.py).  The step loop ends at the
+ * first failure -- σ² < 0 at a Newton iterate of the inner solve (bit 1; the solve itself runs to
+ * its end, and its work past that iterate is not the reference's, which has thrown) or at an
+ * observation point (bit 1: the kernel tests σ² ahead of the draw with either observable.  The
+ * reference's Monte-Carlo observable draws with gradient and never takes σ, so it -- and the oracle
+ * -- fail there in the draw's factor, whose first pivot σ² is: PosDefException, bit 2.  Same step,
+ * same outputs, another bit), a draw whose covariance is not positive definite with σ² ≥ 0 (bit 2),
+ * update_cholesky! (bit 4), a multistart whose candidates are all NaN (bit 8) -- and the adjoint
+ * does not run: values, grad_x, grad_theta and every obs entry
+ * are NaN, counters 3 and 4 are 0, counters 0..2 hold the Newton work done so far, and policy_x
+ * holds x_0..x_k, k the last step whose policy point was found (a failure inside the inner solve of
+ * step k + 1, or at step k itself); the columns after x_k are NOT written and keep the caller's
+ * bytes.  Bit 16 is raised by the adjoint itself, after the step loop and the observations:
+ * values, grad_x and grad_theta are NaN, obs and policy_x are complete, and counters 3 and 4 hold
+ * the adjoint work done (≥ 1 rich evaluation).  No failure touches another trajectory's outputs.
  * Launches on `stream` (hipStream_t, may be NULL) and returns without synchronising.       */
 int mrbo_simulate_mc(mrbo_plan_t* plan, const double* x0s, const double* rnstream, const double* xstarts,
                      const double* dual_y_dx, const double* replay_x, double* values, double* grad_x,
@@ -256,6 +271,11 @@ int mrbo_adam_step(mrbo_plan_t* plan, const double* eto, double* x0s, int32_t* a
  *   result   int32[3]: iterations launched, the iteration after which no restart was active (or
  *            the iterations launched), the OR of every launch's trajectory status bits (non-zero:
  *            the reference would have thrown -- the Julia method throws)
+ * A status bit ends the ascent: like the stop flags, the bits of iteration j are read two iterations
+ * behind the launches, so at most two more iterations follow the first one that carried a bit, and
+ * result[2] holds theirs too.  x0s, eto and active are then those of the plain calls
+ * [mrbo_simulate_mc, mrbo_eto_reduce, the step] repeated result[0] times: a restart with a failed
+ * trajectory has a NaN ETO row, and the step moves its x0 to NaN (x += η·NaN).
  * Arrays are device pointers unless MRBO_FLAG_HOST_POINTERS (then staged once for the whole
  * ascent); synchronises `stream` before returning.                                            */
 typedef enum {

@@ -197,7 +197,7 @@ def eval_base(osur, xs, theta=0.0, sigma_tol=1e-8, rule="EI", cost=None, lbs=Non
 def simulate_mc(osur, x0s, rnstream, xstarts, lbs, ubs, h, theta=0.0, dual_y_dx=None, replay_x=None,
                 max_iters=50, max_ls=20, x_tol=1e-3, f_tol=1e-3, g_tol=1e-8, htol=1e-4, sigma_tol=1e-8,
                 seed=1906, with_gradient=True, nthreads=0, want_policy=True, sample_offset=0,
-                samples_total=0, rule="EI", ghq=None, cost=None, want_kappa=False):
+                samples_total=0, rule="EI", ghq=None, cost=None, want_kappa=False, policy_fill=0.0):
     """Run the oracle's simulate_trajectory_mc for every restart column of x0s (d×R).
     ghq=(nodes, weights), each M×(h+1): the Gauss–Hermite estimator (rbo_simulate_ghq) instead
     of the rnstream draws (rnstream is then only used for its M).
@@ -205,7 +205,9 @@ def simulate_mc(osur, x0s, rnstream, xstarts, lbs, ubs, h, theta=0.0, dual_y_dx=
     want_kappa: also return "kappa" (M×R), each trajectory's largest cond₁ of the acquisition
     Hessians its adjoint solved with (rbo_params.kappa; 1 when none), "vbound" (M×R) the first-order
     bound on the rounding difference of its value and "ylip" (M×R) max_k ‖∂y_k/∂x_k‖₁
-    (rbo_params.vbound / ylip)."""
+    (rbo_params.vbound / ylip).
+    policy_fill: what "policy_x" holds before the run -- a failed trajectory (status != 0) writes the
+    columns up to its last step only and leaves the later ones as they were."""
     x0s, xstarts = _f64(x0s), _f64(xstarts)
     lbs, ubs = _f64(lbs), _f64(ubs)
     d, R = x0s.shape
@@ -235,7 +237,7 @@ def simulate_mc(osur, x0s, rnstream, xstarts, lbs, ubs, h, theta=0.0, dual_y_dx=
     grad_x = np.zeros((d, M, R), order="F")
     grad_t = np.zeros((1, M, R), order="F")
     status = np.zeros((M, R), dtype=np.int32, order="F")
-    policy = np.zeros((d, h + 1, M, R), order="F") if want_policy else None
+    policy = np.full((d, h + 1, M, R), float(policy_fill), order="F") if want_policy else None
     obs = np.zeros((h + 1, M, R), order="F")
     eto = np.zeros((2 + 2 * d + 2, R), order="F")
     evals = np.zeros((3, M, R), dtype=np.int64, order="F")   # [grad, value, hess] per trajectory
