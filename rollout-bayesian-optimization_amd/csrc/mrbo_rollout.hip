@@ -14,6 +14,7 @@
 
 #include "mrbo_device.h"
 #include "bcast_asm.h"
+#include "mrbo_lane_tables.h"
 
 #ifndef MRBO_WAVES_PER_SIMD
 #define MRBO_WAVES_PER_SIMD 2
@@ -98,7 +99,13 @@ struct Lay {
   static constexpr int U_HF = U_UB + D;                  // fantasy rows: [x - X_r (D), g1, g2]  FMAX×(D+2)
   static constexpr int U_STAMP = U_HF + FMAX * (D + 2);   // cycle accumulators (MRBO_STAMPS)
   static constexpr int U_KC = U_STAMP + NSTAMP_SLOTS;             // launch constants (KC_*), see wave_setup
-  static constexpr int U_SIZE = ((U_KC + 15) + 1) & ~1;
+  // lane index words (mrbo_lane_tables.h), 32-bit each: the square layout (one row per lane, full- and
+  // half-wave kernels).  The other layouts unrank in place as before and have no table: with two rows
+  // per lane the table's 144 B per wave cost C4 a wave per workgroup (7 -> 6 of the 160 KB, +10.7 %
+  // per step); the L2-fed layouts (RPL > 2): DESIGN.md §2
+  static constexpr bool LTAB = (RPL == 1);
+  static constexpr int U_TAB = ((U_KC + 15) + 1) & ~1;
+  static constexpr int U_SIZE = LTAB ? ((U_TAB + LaneTables<D, FMAX>::DOUBLES + 1) & ~1) : U_TAB;
   static constexpr int G12 = 3 * NRL;                    // per-lane [g1, g2, Y0] of the base rows
   static constexpr int EC = SQ ? (2 * FMAX + 1) * NRL : 0;  // E (FMAX×NRL) + C ((FMAX+1)×NRL) in LDS
   static constexpr int WAVE_LDS = BROWS * BS + REDN + U_SIZE + G12 + EC;
@@ -620,6 +627,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   double* U = W.U;
   double* B = W.B;
   double* red = W.red;
+  const unsigned* tab = reinterpret_cast<const unsigned*>(U + Ly::U_TAB);   // lane index words
   const bool all_cols = (mode != EV_VALUE);   // gradient columns
   const bool do_val = (mode != EV_GRADC);     // value part: column 0, μ, σ, EI (GRADC keeps the
                                               // preceding VALUE evaluation's, bit-identical)
@@ -919,7 +927,12 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     // entry t = (r, c) per lane; d > 10 has more entries than lanes: lane, lane + 64, …
     for (int t = lane; t < (FMAX * D <= Ly::LANES ? Ly::LANES : FMAX * D); t += Ly::LANES) {
       if (t >= nf * ncol) break;
-      const int r = t / ncol, c = 1 + t % ncol;
+      int r = t / ncol, c = 1 + t % ncol;
+      if constexpr (Ly::LTAB) {   // the same pair from the table
+        const unsigned tw = tab[t];
+        r = lane_field(tw, LaneWord::R, LaneWord::W3);
+        c = lane_field(tw, LaneWord::C, LaneWord::W5);
+      }
       double y = red[Ly::R_MF + D + r * D + (c - 1)];
       for (int q = 0; q <= r; ++q) y = fma(U[Ly::U_DINV + r * FMAX + q], B[(Ly::FR0 + q) * BS + c], y);
       U[Ly::U_YFV + r * D1 + c] = y;
@@ -930,10 +943,17 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   // ---- Gram (incl. fantasy rows) and ∇μ  (lanes own entries; G00 and μ above)
   {
     auto gram_entry = [&](int t) {
-      int a = 0, rem = t;
+      int a = 0, b;   // (a, b) = tri_unrank(D1, t): from the table, or unranked here
+      if constexpr (Ly::LTAB) {
+        const unsigned tw = tab[t];
+        a = lane_field(tw, LaneWord::GA, LaneWord::W5);
+        b = lane_field(tw, LaneWord::GB, LaneWord::W5);
+      } else {
+        int rem = t;
 #pragma unroll
-      for (int aa = 0; aa < D1; ++aa) if (a == aa && rem >= D1 - aa) { rem -= D1 - aa; a = aa + 1; }
-      const int b = a + rem;
+        for (int aa = 0; aa < D1; ++aa) if (a == aa && rem >= D1 - aa) { rem -= D1 - aa; a = aa + 1; }
+        b = a + rem;
+      }
       double g = (mode == EV_GSTART) ? W.GTAB[kst * Ly::NG + t] : red[Ly::R_G + t - 1];
       for (int r = 0; r < nf; ++r) g = fma(U[Ly::U_YFV + r * D1 + a], U[Ly::U_YFV + r * D1 + b], g);
       U[Ly::U_G + a * D1 + b] = g;
@@ -1223,10 +1243,17 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   STAMP(W, 6);
   for (int he = lane; he < (Ly::NH <= Ly::LANES ? Ly::LANES : Ly::NH); he += Ly::LANES) {   // d > 10: lane-strided
     if (he >= Ly::NH) break;
-    int a = 0, rem = he;
+    int a = 0, b;   // (a, b) = tri_unrank(D, he): from the table, or unranked here
+    if constexpr (Ly::LTAB) {
+      const unsigned tw = tab[he];
+      a = lane_field(tw, LaneWord::HA, LaneWord::W5);
+      b = lane_field(tw, LaneWord::HB, LaneWord::W5);
+    } else {
+      int rem = he;
 #pragma unroll
-    for (int aa = 0; aa < D; ++aa) if (a == aa && rem >= D - aa) { rem -= D - aa; a = aa + 1; }
-    const int b = a + rem;
+      for (int aa = 0; aa < D; ++aa) if (a == aa && rem >= D - aa) { rem -= D - aa; a = aa + 1; }
+      b = a + rem;
+    }
     const double gma = U[Ly::U_GMU + a], gmb = U[Ly::U_GMU + b];
     const double gsa = U[Ly::U_GSIG + a], gsb = U[Ly::U_GSIG + b];
     const double rdiag = red[Ly::NH];
@@ -2721,6 +2748,10 @@ __device__ __forceinline__ void wave_setup(WaveCtx<D, RPL, HW>& W, const KParams
   // zero this wave's LDS so that padded rows read as zeros
   for (int q = W.lane; q < Ly::WAVE_LDS; q += Ly::LANES) wbase[q] = 0.0;
   wave_sync();
+  if constexpr (Ly::LTAB) {   // which Gram / Hessian entry and which fantasy (row, column) an index owns: unranked once, here
+    unsigned* tab = reinterpret_cast<unsigned*>(W.U + Ly::U_TAB);
+    for (int t = W.lane; t < LaneTables<D, FMAX>::NT; t += Ly::LANES) tab[t] = lane_word<D, FMAX>(t);
+  }
   if (W.lane == 0) {
     double* kc = W.U + Ly::U_KC;
     kc[KC_PSI0] = kp.psi0;
