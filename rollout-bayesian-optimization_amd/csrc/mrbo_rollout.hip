@@ -10,6 +10,7 @@
 //   gradient(T)           rollout.jl:126-277 (adjoint back-substitution, sparse δK)
 // Numerics follow the reference formulas; the triangular solves use the explicit inverse
 // factor L⁻¹ = [[L0⁻¹,0],[E,Dinv]] instead of substitution (same maths, fp64).
+#include <type_traits>
 #include <utility>
 
 #include "mrbo_device.h"
@@ -612,7 +613,7 @@ constexpr int EV_RT = -1;
 template <int D, int RPL, int HW, int MODE = EV_RT>
 __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int mode_rt,
                                         LaneRes<D, RPL, HW>& lr, int kst = 0, bool back_after = false,
-                                        NewtonState* nt = nullptr) {
+                                        NewtonState* nt = nullptr, bool draw_back = true) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1, BS = Ly::BS, NR = Ly::NR;
   constexpr bool FUSABLE = Ly::SQ && HW == 1;
@@ -631,6 +632,13 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   const bool all_cols = (mode != EV_VALUE);   // gradient columns
   const bool do_val = (mode != EV_GRADC);     // value part: column 0, μ, σ, EI (GRADC keeps the
                                               // preceding VALUE evaluation's, bit-identical)
+  // the fantasy rows' Hessian terms (U_HF) and the acquisition rule with its gradients: nothing of
+  // it is read after a draw evaluation.  The base rows' [g1, g2, Y0] (G12) have no reader there
+  // either but are stored all the same: without the stores the compiler contracts 1 + c·ρ of
+  // rad_eval2's g1 differently and the draw's ∇y moves in its last bits.
+  // The LDS-resident layouts (one or two rows per lane) only: the L2-fed kernels (four and eight
+  // rows per lane) were slower without this work (C5 + cost +1.7 %) and keep it
+  const bool keep = (mode != EV_DRAW) || !Ly::BC;
   STAMP(W, 8);
 
   double x[D];
@@ -706,7 +714,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     row[0] = psi;
 #pragma unroll
     for (int a = 0; a < D; ++a) row[1 + a] = g1 * r[a];
-    {
+    if (keep) {
       double* hf = U + Ly::U_HF + lane * (D + 2);
 #pragma unroll
       for (int a = 0; a < D; ++a) hf[a] = r[a];
@@ -989,6 +997,14 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   const double var = KCV(PSI0) - g00_v;
   double sig, isig;
   sig_isig(var, sig, isig);
+  isig_f = isig;
+  if (!keep) {   // a draw evaluation: σ², σ, 1/σ for the status test, the observable and ∇σ below
+    if (lane == 0) {
+      U[Ly::U_SC + SC_SIG] = sig;
+      U[Ly::U_SC + SC_ISIG] = isig;
+      U[Ly::U_SC + SC_VAR] = var;
+    }
+  } else {
   const double fmin = U[Ly::U_FMIN + S + 1];
   const EIp e = rule_partials(kp.rule, mu, sig, KCV(THETA), fmin, KCV(SIGTOL), isig);
   double alpha = e.g;
@@ -1034,8 +1050,8 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     }
     return 0;
   }
-  isig_f = isig;
   e_f = e;
+  }
   } else {   // GRADC: σ and the EI partials of the VALUE pass at this point
     isig_f = U[Ly::U_SC + SC_ISIG];
     e_f.gmu = U[Ly::U_SC + SC_GMU];
@@ -1047,6 +1063,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     const double gs = -U[Ly::U_G + (1 + lane) * D1] * isig_f;  // ∇σ = -(∇kx·w)/σ
     const double gm = U[Ly::U_GMU + lane];
     U[Ly::U_GSIG + lane] = gs;
+    if (keep) {
     double gal = e_f.gmu * gm + e_f.gsig * gs;                         // ∇αx :567
     double mix = gm * e_f.gmuth + gs * e_f.gsigth;                     // d2α_dxdθ :575-577
     if (kp.cost) {   // ∇(α/c) = ∇α/c − α∇c/c²,  ∂∇(α/c)/∂θ = ∂∇α/∂θ/c − g_θ∇c/c²
@@ -1059,6 +1076,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     }
     U[Ly::U_GAL + lane] = gal;
     U[Ly::U_MIX + lane] = mix;
+    }
   }
   if (mode == EV_GRAD || mode == EV_GRADC || mode == EV_GSTART) {   // a BACK evaluation may follow
     wave_sync();
@@ -1075,6 +1093,8 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     for (int s = 0; s < RPL; ++s) acc[s][0] = W.G12[3 * (lane + WAVE * s) + 2];
   }
   wave_sync();   // U_SC / gradients of the front part visible to all lanes
+  // the last step's draw: no surface follows, so nothing reads w, w_f (condition's new row)
+  if (mode == EV_DRAW && !draw_back) { STAMP(W, 4); STAMP(W, 5); return 0; }
   EIp e;
   e.gmu = U[Ly::U_SC + SC_GMU];
   e.gsig = U[Ly::U_SC + SC_GSIG];
@@ -1285,10 +1305,13 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
 // ================================================================================
 // condition!(fs, x, y) -- radial_basis_surrogates.jl:431-441, after an EV_DRAW eval at x
 // on surface S = nf-1.  Appends the inverse-factor row and the new coefficient vector.
+// last: the trajectory's last step.  No evaluation on the new surface follows, so only the pivot
+// test and what the resolve and the adjoint read of the new point remain: y (U_YF), x (U_XF) and,
+// of step 0 alone, ∇y (U_GF).
 // ================================================================================
 template <int D, int RPL, int HW>
 __device__ __forceinline__ int condition(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, double yv, const double* gy,
-                         const LaneRes<D, RPL, HW>& lr) {
+                         const LaneRes<D, RPL, HW>& lr, bool last = false) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int NR = Ly::NR;
   double* U = W.U;
@@ -1298,6 +1321,18 @@ __device__ __forceinline__ int condition(WaveCtx<D, RPL, HW>& W, const KParams& 
   const double mu = U[Ly::U_SC + SC_MU];
   const double l22sq = KCV(PSI0) + KCV(SN2) - g00;   // C - L21·L21 (update_cholesky! :405-418)
   if (!(l22sq > 0.0)) return 4;                  // PosDefException
+  if (last) {
+    if (lane == nf) U[Ly::U_YF + nf] = yv;
+    if (lane < D) U[Ly::U_XF + nf * D + lane] = U[Ly::U_X + lane];
+    if (nf == 0) {   // h = 0: ∇y₀ is the trajectory's ∇x when step 0 is the best step
+      double g0 = 0.0;
+#pragma unroll
+      for (int a = 0; a < D; ++a) g0 = (a == lane) ? gy[a] : g0;
+      if (lane < D) U[Ly::U_GF + lane] = g0;
+    }
+    wave_sync();
+    return 0;
+  }
   const double inv = 1.0 / sqrt(l22sq);
   const double gam = (yv - mu) / l22sq;          // c_new = [c - γ w; γ]
 #pragma unroll
@@ -1365,9 +1400,10 @@ __device__ __forceinline__ int draw_factor(WaveCtx<D, RPL, HW>& W, double (&Lc)[
 // gp_draw with gradient (r_b_s.jl:588-611): [y;∇y] = [μ;∇μ] + chol(Dk(0) − G)·z.
 // hdr: null, or the restart-table header of this trajectory's restart (k = 0): the factor and
 // whether it failed come from there instead of being computed.
+// y_only (a last step k > 0, whose ∇y nobody reads): the factor in full, for the status, and y alone.
 template <int D, int RPL, int HW>
 __device__ __forceinline__ int draw(WaveCtx<D, RPL, HW>& W, const KParams& kp, const double* z, double& yv, double* gy,
-                                    const double* hdr = nullptr) {
+                                    const double* hdr = nullptr, bool y_only = false) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1;
   const double* U = W.U;
@@ -1382,6 +1418,13 @@ __device__ __forceinline__ int draw(WaveCtx<D, RPL, HW>& W, const KParams& kp, c
   }
   double out[D1];
   out[0] = U[Ly::U_SC + SC_MU];
+  if (y_only) {
+    double s = 0.0;
+    s += Lc[0] * z[0];
+    out[0] += s;
+    yv = out[0];
+    return 0;
+  }
 #pragma unroll
   for (int a = 0; a < D; ++a) out[1 + a] = U[Ly::U_GMU + a];
 #pragma unroll
@@ -1971,9 +2014,35 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
 #pragma unroll
   for (int r = 0; r < FMAX; ++r) ae[r] = 0.0;
   const double* cS = W.C + (long long)(S + 1) * Ly::NRL;
-  // all FMAX rows unconditionally (rows ≥ nf hold finite stale values, masked below): a load
-  // under a condition would become a branch with a full LDS round trip per row.  Rows N..NR-1
-  // of the tables are zero.
+  // Packed layouts: all FMAX rows unconditionally (rows ≥ nf hold finite stale values, masked
+  // below): a load under a condition would become a branch with a full LDS round trip per row.
+  // Square layout: one copy of the row loop per nf (wave-uniform, 1..FMAX) with nf accumulators
+  // and nf row loads; ae[r ≥ nf] stay zero and are not read.  Each ae[r] is a chain of its own,
+  // the same in every copy.  Rows N..NR-1 of the tables are zero.
+  auto sq_rows = [&](auto nfc) {
+    constexpr int NF = decltype(nfc)::value;
+    if (split) {
+#pragma unroll 8
+      for (int j = 0; j < NR / 2; ++j) {
+        const int i = 2 * j + hf;
+        const double kv = W.KXB[i * ns + k];
+        amu = fma(cS[i], kv, amu);
+#pragma unroll
+        for (int r = 0; r < NF; ++r) ae[r] = fma(W.E[(long long)r * Ly::NRL + i], kv, ae[r]);
+      }
+      amu = swap_fold<32>(amu, amu);
+#pragma unroll
+      for (int r = 0; r < NF; ++r) ae[r] = swap_fold<32>(ae[r], ae[r]);
+    } else {
+#pragma unroll 8
+      for (int i = 0; i < W.N; ++i) {
+        const double kv = W.KXB[i * ns + k];
+        amu = fma(cS[i], kv, amu);
+#pragma unroll
+        for (int r = 0; r < NF; ++r) ae[r] = fma(W.E[(long long)r * Ly::NRL + i], kv, ae[r]);
+      }
+    }
+  };
   if constexpr (!Ly::SQ) {
     // packed layouts (E, c and the kernel-row table in global memory): lanes own data rows and
     // the starts run in a loop, so every load is a coalesced row walk (a lane-per-start loop over
@@ -2032,25 +2101,21 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
 #pragma unroll
     for (int r = 0; r < FMAX; ++r) ae[r] = sums[8 * k + 1 + r];
     wave_sync();   // sums read before the scratch is reused
-  } else if (split) {
-#pragma unroll 8
-    for (int j = 0; j < NR / 2; ++j) {
-      const int i = 2 * j + hf;
-      const double kv = W.KXB[i * ns + k];
-      amu = fma(cS[i], kv, amu);
-#pragma unroll
-      for (int r = 0; r < FMAX; ++r) ae[r] = fma(W.E[(long long)r * Ly::NRL + i], kv, ae[r]);
-    }
-    amu = swap_fold<32>(amu, amu);
-#pragma unroll
-    for (int r = 0; r < FMAX; ++r) ae[r] = swap_fold<32>(ae[r], ae[r]);
   } else {
-#pragma unroll 8
-    for (int i = 0; i < W.N; ++i) {
-      const double kv = W.KXB[i * ns + k];
-      amu = fma(cS[i], kv, amu);
-#pragma unroll
-      for (int r = 0; r < FMAX; ++r) ae[r] = fma(W.E[(long long)r * Ly::NRL + i], kv, ae[r]);
+    static_assert(FMAX == 4 || FMAX == 6, "batch_start_values: one row-loop copy per nf");
+    switch (nf) {
+      case 0: sq_rows(std::integral_constant<int, 0>{}); break;   // base_solve: the base surface alone
+      case 1: sq_rows(std::integral_constant<int, 1>{}); break;
+      case 2: sq_rows(std::integral_constant<int, 2>{}); break;
+      case 3: sq_rows(std::integral_constant<int, 3>{}); break;
+      default:
+        if constexpr (FMAX == 4) {
+          sq_rows(std::integral_constant<int, 4>{});
+        } else {
+          if (nf == 4) sq_rows(std::integral_constant<int, 4>{});
+          else if (nf == 5) sq_rows(std::integral_constant<int, 5>{});
+          else sq_rows(std::integral_constant<int, 6>{});
+        }
     }
   }
   double pf[FMAX];
@@ -2545,7 +2610,11 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
       tabled = (k == 0) && kp.rtab != nullptr;
       if (tabled) restart_row_load<D, RPL, HW>(W, kp, r, lr);
     }
-    if (!tabled) evaluate<D, RPL, HW>(W, kp, S, EV_DRAW, lr);
+    // the last step conditions no surface: its evaluation stops before the backward product, its
+    // draw forms y alone (∇y_k is read for k < t ≤ h only, and ∇y₀ when step 0 is the best) and
+    // its condition keeps the pivot test, y and x (the LDS-resident layouts, as evaluate's `keep`)
+    const bool last = Ly::BC && (k == h), y_only = last && k > 0;
+    if (!tabled) evaluate<D, RPL, HW>(W, kp, S, EV_DRAW, lr, 0, false, nullptr, !last);
     if (U[Ly::U_SC + SC_VAR] < 0.0) { st |= 1; break; }
     if (k == 0 && lane < D) U[Ly::U_GMU0 + lane] = U[Ly::U_GMU + lane];
     double yv, gy[D];
@@ -2555,17 +2624,19 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
       const long long ik = (long long)m + (long long)M * k;
       const double tk = kp.ghq_nodes[ik], wk = kp.ghq_w[ik];
       yv = U[Ly::U_SC + SC_MU] + 1.4142135623730951 * U[Ly::U_SC + SC_SIG] * tk;
+      if (!y_only) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) gy[a] = wk * (U[Ly::U_GMU + a] + 1.4142135623730951 * U[Ly::U_GSIG + a] * tk);
+        for (int a = 0; a < D; ++a) gy[a] = wk * (U[Ly::U_GMU + a] + 1.4142135623730951 * U[Ly::U_GSIG + a] * tk);
+      }
     } else {
       double z[D1];
 #pragma unroll
       for (int a = 0; a < D1; ++a) z[a] = kp.rn[(long long)m + (long long)M * a + (long long)M * D1 * k];
-      st |= draw<D, RPL, HW>(W, kp, z, yv, gy, tabled ? W.red : nullptr);
+      st |= draw<D, RPL, HW>(W, kp, z, yv, gy, tabled ? W.red : nullptr, y_only);
       if (st) break;
     }
     wave_sync();
-    st |= condition<D, RPL, HW>(W, kp, S, yv, gy, lr);
+    st |= condition<D, RPL, HW>(W, kp, S, yv, gy, lr, last);
     STAMP(W, 10);
     if (st) break;
   }
