@@ -514,6 +514,29 @@ __device__ __forceinline__ void wave_reduce_n(F&& fill, int n, double* red, int 
   }
 }
 
+// f(std::integral_constant<int, nf>{}) for the run-time, wave-uniform number of fantasy rows
+// nf = 0..FMAX: one copy of f's body per row count (evaluate's fantasy-row phases on the square
+// full-wave layout, as batch_start_values' row loop).  A copy sums the terms of rows r < nf in the
+// order the run-time form does, so the copies differ from it in instructions only, not in bits.
+template <class F>
+__device__ __forceinline__ void nf_switch(int nf, F&& f) {
+  static_assert(FMAX == 4 || FMAX == 6, "nf_switch: one arm per nf");
+  switch (nf) {
+    case 0: f(std::integral_constant<int, 0>{}); break;   // base_solve, the step-0 draw: the base surface alone
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default:
+      if constexpr (FMAX == 4) {
+        f(std::integral_constant<int, 4>{});
+      } else {
+        if (nf == 4) f(std::integral_constant<int, 4>{});
+        else if (nf == 5) f(std::integral_constant<int, 5>{});
+        else f(std::integral_constant<int, 6>{});
+      }
+  }
+}
+
 // The same product with this lane's L entries from global memory (L2-resident image):
 // step n of the block at lb[n·64].  All 64 steps of both row blocks of a pass are loaded into
 // registers before their FMAs (the image is zero-padded, so the loads need no bounds).
@@ -617,6 +640,11 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1, BS = Ly::BS, NR = Ly::NR;
   constexpr bool FUSABLE = Ly::SQ && HW == 1;
+  // NFC: the phases below that walk the fantasy rows run one copy per nf (nf_switch) with exactly
+  // nf rows' loads and FMAs and no select on r < nf.  nf is wave-uniform on this layout alone (the
+  // half-wave kernel's halves sit on different surfaces), and the layouts with more rows per lane
+  // keep the run-time form, as do the Gram and ∇μ entries, whose copies were slower
+  constexpr bool NFC = FUSABLE;
   static_assert(MODE == EV_RT || (MODE >= EV_VALUE && MODE <= EV_GSTART), "evaluate: MODE");
   const int mode = MODE == EV_RT ? mode_rt : MODE;   // a constant expression when MODE is fixed
   // Opaque copy of the lane index: keeps the per-lane LDS/global addresses derived from it
@@ -646,14 +674,22 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   for (int a = 0; a < D; ++a) x[a] = U[Ly::U_X + a];
 
   // base coefficients of surface S and this lane's entries of the fantasy inverse-factor rows
+  // (NFC: Ev[·][r ≥ nf] is neither loaded nor read)
   double Ev[RPL][FMAX];
 #pragma unroll
   for (int s = 0; s < RPL; ++s) {
     lr.cb[s] = W.C[(long long)(S + 1) * Ly::NRL + lane + WAVE * s];
+    if constexpr (NFC) {
+      nf_switch(nf, [&](auto nfc) {
 #pragma unroll
-    for (int r = 0; r < FMAX; ++r) Ev[s][r] = W.E[(long long)r * Ly::NRL + lane + WAVE * s];   // unconditional
+        for (int r = 0; r < decltype(nfc)::value; ++r) Ev[s][r] = W.E[(long long)r * Ly::NRL + lane + WAVE * s];
+      });
+    } else {
 #pragma unroll
-    for (int r = 0; r < FMAX; ++r) Ev[s][r] = (r < nf) ? Ev[s][r] : 0.0;
+      for (int r = 0; r < FMAX; ++r) Ev[s][r] = W.E[(long long)r * Ly::NRL + lane + WAVE * s];   // unconditional
+#pragma unroll
+      for (int r = 0; r < FMAX; ++r) Ev[s][r] = (r < nf) ? Ev[s][r] : 0.0;
+    }
   }
 
   const int N = W.N;
@@ -839,6 +875,21 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   // ---- 3. per-lane products and wave reductions
   if (do_val) {   // [|v|² = kx'K⁻¹kx, μ = kx·c (base parts), E_r·kx (r < nf)]: 2 + nf values
     static_assert(2 + FMAX <= 8, "value reduction: one chunk");
+    if constexpr (NFC) {   // a copy per nf: the chunk of 2 + nf values is a constant
+      nf_switch(nf, [&](auto nfc) {
+        constexpr int NF = decltype(nfc)::value;
+        wave_reduce_n<HW, 1>([&](int t) {
+          double s_ = 0.0;
+#pragma unroll
+          for (int s = 0; s < RPL; ++s) {
+            if (t == 0) s_ = fma(acc[s][0], acc[s][0], s_);
+            else if (t == 1) s_ = fma(lr.cb[s], Bown[s][0], s_);
+            else if (t - 2 < NF) s_ = fma(Ev[s][t - 2], Bown[s][0], s_);
+          }
+          return s_;
+        }, 2 + NF, red + Ly::R_VAL, lane);
+      });
+    } else {
     wave_reduce_n<HW, 1>([&](int t) {
       double s_ = 0.0;
 #pragma unroll
@@ -849,6 +900,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       }
       return s_;
     }, 2 + nf, red + Ly::R_VAL, lane);
+    }
   }
   if (all_cols) {
     // Gram entries (a ≤ b) except (0,0); GSTART takes them from the start tables
@@ -875,6 +927,25 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     }
     // ∇μ and fantasy cross products for the gradient columns
     // (fantasy rows ≥ nf carry nothing: D·(1 + nf) values)
+    if constexpr (NFC) {   // a copy per nf: the chunks of D·(1 + nf) values are constants
+      nf_switch(nf, [&](auto nfc) {
+        constexpr int NF = decltype(nfc)::value;
+        wave_reduce_n<HW, Ly::NMFC>([&](int t) {
+          double s_ = 0.0;
+          if (t < D * (1 + NF)) {
+            const int grp = t / D, a = t % D;  // grp 0: c ; grp r+1: E_r
+            if (grp == 0) {
+#pragma unroll
+              for (int s = 0; s < RPL; ++s) s_ = fma(lr.cb[s], Bown[s][1 + a], s_);
+            } else {
+#pragma unroll
+              for (int s = 0; s < RPL; ++s) s_ = fma(Ev[s][grp - 1], Bown[s][1 + a], s_);
+            }
+          }
+          return s_;
+        }, D * (1 + NF), red + Ly::R_MF, lane);
+      });
+    } else {
     wave_reduce_n<HW, Ly::NMFC>([&](int t) {
       double s_ = 0.0;
       if (t < Ly::NMF) {
@@ -889,6 +960,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       }
       return s_;
     }, D * (1 + nf), red + Ly::R_MF, lane);
+    }
   }
   wave_sync();
   STAMP(W, 2);
@@ -897,6 +969,57 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   // G00 = |Y0|² + Σ_r Yf[r][0]², μ = c·kx + Σ_r c_r Bf[r][0].  One batch of unconditional LDS
   // reads instead of three dependent lane-distributed phases (same FMA order).
   double mu_v = 0.0, g00_v = 0.0;
+  if constexpr (NFC) {
+  // 4a and 4b in a copy per nf: NF rows of bf, the NF(NF + 1)/2 Dinv FMAs, no select on r < nf
+  nf_switch(nf, [&](auto nfc) {
+  constexpr int NF = decltype(nfc)::value;
+  if (do_val) {
+    double bf[NF > 0 ? NF : 1], yf[NF > 0 ? NF : 1];
+#pragma unroll
+    for (int r = 0; r < NF; ++r) bf[r] = B[(Ly::FR0 + r) * BS];
+    g00_v = red[Ly::R_VAL];
+    mu_v = red[Ly::R_VAL + 1];
+#pragma unroll
+    for (int r = 0; r < NF; ++r) {
+      double y = red[Ly::R_VAL + 2 + r];
+#pragma unroll
+      for (int q = 0; q <= r; ++q) y = fma(U[Ly::U_DINV + r * FMAX + q], bf[q], y);
+      yf[r] = y;
+    }
+#pragma unroll
+    for (int r = 0; r < NF; ++r) {
+      g00_v = fma(yf[r], yf[r], g00_v);
+      mu_v = fma(U[Ly::U_CF + (S + 1) * FMAX + r], bf[r], mu_v);
+    }
+    if (lane < NF) {
+      double mine = 0.0;
+#pragma unroll
+      for (int r = 0; r < NF; ++r) mine = (lane == r) ? yf[r] : mine;
+      U[Ly::U_YFV + lane * D1] = mine;
+    }
+    if (lane == 0) {
+      U[Ly::U_G] = g00_v;
+      U[Ly::U_SC + SC_MU] = mu_v;
+    }
+  }
+  if (all_cols) {
+    const int ncol = D;
+    for (int t = lane; t < (FMAX * D <= Ly::LANES ? Ly::LANES : FMAX * D); t += Ly::LANES) {
+      if (t >= NF * ncol) break;
+      const unsigned tw = tab[t];
+      const int r = lane_field(tw, LaneWord::R, LaneWord::W3);
+      const int c = lane_field(tw, LaneWord::C, LaneWord::W5);
+      double y = red[Ly::R_MF + D + r * D + (c - 1)];
+      // the lane's q ≤ r among the copy's NF rows, masked by the lane's own r
+#pragma unroll
+      for (int q = 0; q < NF; ++q)
+        if (q == 0 || q <= r) y = fma(U[Ly::U_DINV + r * FMAX + q], B[(Ly::FR0 + q) * BS + c], y);
+      U[Ly::U_YFV + r * D1 + c] = y;
+      if constexpr (FMAX * D <= Ly::LANES) break;
+    }
+  }
+  });
+  } else {
   if (do_val) {
     double bf[FMAX], yf[FMAX];
 #pragma unroll
@@ -928,9 +1051,10 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
       U[Ly::U_SC + SC_MU] = mu_v;
     }
   }
+  }
   // ---- 4b. gradient columns of the fantasy rows: Yf = Fpart + Dinv · Bf   (lane = (r, c), c ≥ 1)
   if (all_cols) {
-  {
+  if constexpr (!NFC) {
     const int ncol = D;
     // entry t = (r, c) per lane; d > 10 has more entries than lanes: lane, lane + 64, …
     for (int t = lane; t < (FMAX * D <= Ly::LANES ? Ly::LANES : FMAX * D); t += Ly::LANES) {
@@ -949,6 +1073,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   }
   wave_sync();
   // ---- Gram (incl. fantasy rows) and ∇μ  (lanes own entries; G00 and μ above)
+  // (the run-time row loops here: their per-nf copies were measured slower)
   {
     auto gram_entry = [&](int t) {
       int a = 0, b;   // (a, b) = tri_unrank(D1, t): from the table, or unranked here
@@ -1177,6 +1302,36 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
         }
       }
     }
+    if constexpr (NFC) {
+    // the fantasy part and w_f / P_f in a copy per nf
+    nf_switch(nf, [&](auto nfc) {
+      constexpr int NF = decltype(nfc)::value;
+#pragma unroll
+      for (int s = 0; s < RPL; ++s) {
+#pragma unroll
+        for (int r = 0; r < NF; ++r) {
+          const double er = Ev[s][r];
+          wv[s] = fma(er, U[Ly::U_YFV + r * D1], wv[s]);
+          if (rich) {
+#pragma unroll
+            for (int a = 0; a < D; ++a) pv[s][a] = fma(er, U[Ly::U_YFV + r * D1 + 1 + a], pv[s][a]);
+          }
+        }
+      }
+      const int ncol = rich ? D1 : 1;
+      for (int e = lane; e < (FMAX * D1 <= Ly::LANES ? Ly::LANES : FMAX * D1); e += Ly::LANES) {
+        if (e >= NF * ncol) break;
+        const int q = e / ncol, c = e % ncol;
+        double t = 0.0;
+        // the lane's r ≥ q among the copy's NF rows, masked by the lane's own q
+#pragma unroll
+        for (int r = 0; r < NF; ++r)
+          if (r == NF - 1 || r >= q) t = fma(U[Ly::U_DINV + r * FMAX + q], U[Ly::U_YFV + r * D1 + c], t);
+        if (c == 0) U[Ly::U_WF + q] = t; else U[Ly::U_PF + q * D + c - 1] = t;
+        if constexpr (FMAX * D1 <= Ly::LANES) break;
+      }
+    });
+    } else {
     // fantasy part: + Σ_r E[r][i] Yf[r]
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
@@ -1191,6 +1346,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
         }
       }
     }
+    }
 #pragma unroll
     for (int s = 0; s < RPL; ++s) {
       lr.w[s] = wv[s];
@@ -1199,7 +1355,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     }
   }
   // w_f[q] = Σ_{r ≥ q} Dinv[r][q] Yf[r][0]  (and P_f)
-  {
+  if constexpr (!NFC) {
     const int ncol = rich ? D1 : 1;
     for (int e = lane; e < (FMAX * D1 <= Ly::LANES ? Ly::LANES : FMAX * D1); e += Ly::LANES) {   // d > 9: lane-strided
       if (e >= nf * ncol) break;
@@ -1279,11 +1435,23 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     const double rdiag = red[Ly::NH];
     double hv = red[he] + ((a == b) ? rdiag : 0.0);
     // fantasy data points ([x − X_r, g1, g2] from phase 1)
+    if constexpr (NFC) {   // a copy per nf
+      nf_switch(nf, [&](auto nfc) {
+#pragma unroll
+        for (int r = 0; r < decltype(nfc)::value; ++r) {
+          const double* hf = U + Ly::U_HF + r * (D + 2);
+          const double coef = e.gmu * U[Ly::U_CF + (S + 1) * FMAX + r] - gsig_over * U[Ly::U_WF + r];
+          hv = fma(coef * hf[D + 1], hf[a] * hf[b], hv);
+          if (a == b) hv = fma(coef, hf[D], hv);
+        }
+      });
+    } else {
     for (int r = 0; r < nf; ++r) {
       const double* hf = U + Ly::U_HF + r * (D + 2);
       const double coef = e.gmu * U[Ly::U_CF + (S + 1) * FMAX + r] - gsig_over * U[Ly::U_WF + r];
       hv = fma(coef * hf[D + 1], hf[a] * hf[b], hv);
       if (a == b) hv = fma(coef, hf[D], hv);
+    }
     }
     hv += e.gmumu * gma * gmb + e.gsigsig * gsa * gsb - gsig_over * (gsa * gsb + U[Ly::U_G + (1 + a) * D1 + 1 + b]);
     if (kp.cost) {   // H(α/c) = (Hα − ∇f∇cᵀ − ∇c∇fᵀ)/c − (α/c²)Hc, ∇f = U_GAL (weighted)
