@@ -537,6 +537,15 @@ __device__ __forceinline__ void nf_switch(int nf, F&& f) {
   }
 }
 
+// nf_switch for a caller whose row count may be a template argument: NFIX ≥ 0 is the arm itself, with
+// no dispatch (a whole rollout step of the square full-wave layout runs under one nf_switch, in
+// trajectory()); NFIX = -1 is the run-time switch above.
+template <int NFIX, class F>
+__device__ __forceinline__ void nf_arm(int nf, F&& f) {
+  if constexpr (NFIX >= 0) f(std::integral_constant<int, NFIX>{});
+  else nf_switch(nf, static_cast<F&&>(f));
+}
+
 // The same product with this lane's L entries from global memory (L2-resident image):
 // step n of the block at lb[n·64].  All 64 steps of both row blocks of a pass are loaded into
 // registers before their FMAs (the image is zero-padded, so the loads need no bounds).
@@ -610,8 +619,8 @@ struct NewtonState {
 enum { NT_STOP = 0,        // the iteration ends here
        NT_BACKTRACK = 1,   // projected Armijo failed: the caller halves the step (t is updated)
        NT_CONTINUE = 2 };  // the gradient at x = U_NX is needed
-template <int D, int RPL, int HW>
-__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, NewtonState& ns);
+template <int D, int RPL, int HW, int NFIX = -1>
+__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, NewtonState& ns);
 
 // evaluate<…, MODE = EV_RT>: the mode is not a template argument but the run-time argument
 constexpr int EV_RT = -1;
@@ -633,8 +642,12 @@ constexpr int EV_RT = -1;
 // the mode is the run-time argument mode_rt.  With a fixed MODE, `mode` below and everything derived
 // from it (all_cols, do_val, rows_kept, the product arm, the reductions that run, the exits) are
 // constant expressions: the arms of other modes are never emitted, whatever the inliner does.
-template <int D, int RPL, int HW, int MODE = EV_RT>
-__device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int mode_rt,
+// NFIX: the number of fantasy rows S + 1 as a template argument (the square full-wave layout, from the
+// step's dispatch in trajectory() down), or -1: S is the run-time argument and every fantasy-row
+// phase finds its copy by nf_switch.  With NFIX ≥ 0, S and nf are constant expressions and the phases
+// are their arms, straight-line.
+template <int D, int RPL, int HW, int MODE = EV_RT, int NFIX = -1>
+__device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, int mode_rt,
                                         LaneRes<D, RPL, HW>& lr, int kst = 0, bool back_after = false,
                                         NewtonState* nt = nullptr, bool draw_back = true) {
   using Ly = Lay<D, RPL, HW>;
@@ -646,13 +659,21 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   // keep the run-time form, as do the Gram and ∇μ entries, whose copies were slower
   constexpr bool NFC = FUSABLE;
   static_assert(MODE == EV_RT || (MODE >= EV_VALUE && MODE <= EV_GSTART), "evaluate: MODE");
+  static_assert(NFIX == -1 || (NFC && NFIX >= 0 && NFIX <= FMAX), "evaluate: NFIX");
+  const int S = NFIX >= 0 ? NFIX - 1 : S_rt;   // a constant expression when NFIX is fixed
   const int mode = MODE == EV_RT ? mode_rt : MODE;   // a constant expression when MODE is fixed
   // Opaque copy of the lane index: keeps the per-lane LDS/global addresses derived from it
   // inside this evaluation instead of being hoisted (and held live in VGPRs) across the
   // caller's Newton / horizon loops -- the difference between 1 and 3-4 waves per SIMD.
   int lane = W.lane;
   asm volatile("" : "+v"(lane));
-  const int nf = S + 1;
+  // with NFIX fixed nf itself is an opaque copy of the constant: the copies take NFIX from their
+  // arm, and what reads nf -- the Gram and ∇μ entry loops, whose unrolled copies were slower
+  // (DESIGN.md §8), and two lane tests -- keeps the run-time form's statements, so the layouts
+  // outside the scope compile to the parent's code
+  int nf_o = S + 1;
+  if constexpr (NFIX >= 0) asm volatile("" : "+s"(nf_o));
+  const int nf = nf_o;
   double* U = W.U;
   double* B = W.B;
   double* red = W.red;
@@ -675,12 +696,12 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
 
   // base coefficients of surface S and this lane's entries of the fantasy inverse-factor rows
   // (NFC: Ev[·][r ≥ nf] is neither loaded nor read)
-  double Ev[RPL][FMAX];
+  double Ev[RPL][NFIX > 0 ? NFIX : (NFIX == 0 ? 1 : FMAX)];
 #pragma unroll
   for (int s = 0; s < RPL; ++s) {
     lr.cb[s] = W.C[(long long)(S + 1) * Ly::NRL + lane + WAVE * s];
     if constexpr (NFC) {
-      nf_switch(nf, [&](auto nfc) {
+      nf_arm<NFIX>(nf, [&](auto nfc) {
 #pragma unroll
         for (int r = 0; r < decltype(nfc)::value; ++r) Ev[s][r] = W.E[(long long)r * Ly::NRL + lane + WAVE * s];
       });
@@ -876,7 +897,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   if (do_val) {   // [|v|² = kx'K⁻¹kx, μ = kx·c (base parts), E_r·kx (r < nf)]: 2 + nf values
     static_assert(2 + FMAX <= 8, "value reduction: one chunk");
     if constexpr (NFC) {   // a copy per nf: the chunk of 2 + nf values is a constant
-      nf_switch(nf, [&](auto nfc) {
+      nf_arm<NFIX>(nf, [&](auto nfc) {
         constexpr int NF = decltype(nfc)::value;
         wave_reduce_n<HW, 1>([&](int t) {
           double s_ = 0.0;
@@ -928,7 +949,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     // ∇μ and fantasy cross products for the gradient columns
     // (fantasy rows ≥ nf carry nothing: D·(1 + nf) values)
     if constexpr (NFC) {   // a copy per nf: the chunks of D·(1 + nf) values are constants
-      nf_switch(nf, [&](auto nfc) {
+      nf_arm<NFIX>(nf, [&](auto nfc) {
         constexpr int NF = decltype(nfc)::value;
         wave_reduce_n<HW, Ly::NMFC>([&](int t) {
           double s_ = 0.0;
@@ -971,7 +992,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
   double mu_v = 0.0, g00_v = 0.0;
   if constexpr (NFC) {
   // 4a and 4b in a copy per nf: NF rows of bf, the NF(NF + 1)/2 Dinv FMAs, no select on r < nf
-  nf_switch(nf, [&](auto nfc) {
+  nf_arm<NFIX>(nf, [&](auto nfc) {
   constexpr int NF = decltype(nfc)::value;
   if (do_val) {
     double bf[NF > 0 ? NF : 1], yf[NF > 0 ? NF : 1];
@@ -1164,13 +1185,13 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     STAMP(W, 4);
     if constexpr (FUSABLE) {
       if (nt != nullptr) {
-        nt->why = newton_after_value<D, RPL, HW>(W, kp, S, *nt);
+        nt->why = newton_after_value<D, RPL, HW, NFIX>(W, kp, S, *nt);
         if (nt->why != NT_CONTINUE || !kp.newton_fused) return 0;
         // the iteration continues at this x: GRADC, the projected-gradient test and BACK here, in
         // an instantiation of their own (mode is a compile-time constant in it, and a backward
         // branch into the code above would make this body a loop, whose hoisted invariants spill)
         if constexpr (MODE != EV_GRADC)
-          return EVR_GRAD | evaluate<D, RPL, HW, EV_GRADC>(W, kp, S, EV_GRADC, lr, kst, true);
+          return EVR_GRAD | evaluate<D, RPL, HW, EV_GRADC, NFIX>(W, kp, S, EV_GRADC, lr, kst, true);
       }
     }
     return 0;
@@ -1304,7 +1325,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     }
     if constexpr (NFC) {
     // the fantasy part and w_f / P_f in a copy per nf
-    nf_switch(nf, [&](auto nfc) {
+    nf_arm<NFIX>(nf, [&](auto nfc) {
       constexpr int NF = decltype(nfc)::value;
 #pragma unroll
       for (int s = 0; s < RPL; ++s) {
@@ -1436,7 +1457,7 @@ __device__ __forceinline__ int evaluate(WaveCtx<D, RPL, HW>& W, const KParams& k
     double hv = red[he] + ((a == b) ? rdiag : 0.0);
     // fantasy data points ([x − X_r, g1, g2] from phase 1)
     if constexpr (NFC) {   // a copy per nf
-      nf_switch(nf, [&](auto nfc) {
+      nf_arm<NFIX>(nf, [&](auto nfc) {
 #pragma unroll
         for (int r = 0; r < decltype(nfc)::value; ++r) {
           const double* hf = U + Ly::U_HF + r * (D + 2);
@@ -1832,13 +1853,14 @@ __device__ __forceinline__ bool grad_certified(const WaveCtx<D, RPL, HW>& W, con
 // row (G12) and fantasy row (U_HF) is still in LDS -- the same bits a new radial evaluation
 // would give; only ρ is recomputed.
 // With a cost model (f = α/c, araw = α at x) every bound B on |∂α| becomes B/c + |α| max|∇c|/c².
-template <int D, int RPL, int HW, bool ROWS_KEPT = false>
-__device__ __forceinline__ bool tight_certified(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, double gm, double gs,
+template <int D, int RPL, int HW, bool ROWS_KEPT = false, int NFIX = -1>
+__device__ __forceinline__ bool tight_certified(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, double gm, double gs,
                                                 double sig, double isig, double araw = 0.0) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int NR = Ly::NR;
   const double* U = W.U;
   const int lane = W.ln();
+  const int S = NFIX >= 0 ? NFIX - 1 : S_rt;   // NFIX: as evaluate's
   const int nf = S + 1;
   double isc = 1.0, add = 0.0;
   if (kp.cost) {
@@ -1892,9 +1914,10 @@ __device__ __forceinline__ bool tight_certified(WaveCtx<D, RPL, HW>& W, const KP
 // accept (U_NX moves, ‖Δx‖∞ and |Δf| tests, ++it) -- then the iteration limit, the NaN exit and the
 // two gradient certificates.  One inlined copy per kernel: inside evaluate() on the square
 // full-wave layout (evaluate's nt), in newton() elsewhere.
-template <int D, int RPL, int HW>
-__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, NewtonState& ns) {
+template <int D, int RPL, int HW, int NFIX>
+__device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, NewtonState& ns) {
   using Ly = Lay<D, RPL, HW>;
+  const int S = NFIX >= 0 ? NFIX - 1 : S_rt;   // NFIX: as evaluate's
   double* U = W.U;
   const int lane = W.ln();
   if (U[Ly::U_SC + SC_VAR] < 0.0) ns.st |= 1;
@@ -1930,7 +1953,7 @@ __device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const 
   if (ns.f != ns.f) return NT_STOP;
   if (grad_certified<D, RPL, HW>(W, kp)) return NT_STOP;     // ‖∇α‖ ≤ g_tol guaranteed: stationary
   if (kp.gcert_sig > 0.0 &&
-      tight_certified<D, RPL, HW, true>(W, kp, S, U[Ly::U_SC + SC_GMU], U[Ly::U_SC + SC_GSIG], U[Ly::U_SC + SC_SIG],
+      tight_certified<D, RPL, HW, true, NFIX>(W, kp, S, U[Ly::U_SC + SC_GMU], U[Ly::U_SC + SC_GSIG], U[Ly::U_SC + SC_SIG],
                                     U[Ly::U_SC + SC_ISIG], kp.cost ? U[Ly::U_SC + SC_ARAW] : 0.0))
     return NT_STOP;
   STAMP(W, 20);
@@ -1945,7 +1968,8 @@ __device__ __forceinline__ int newton_after_value(WaveCtx<D, RPL, HW>& W, const 
 // step is taken.  Values and gradients are bit-identical to a FULL evaluation at the same
 // point (same code path), so the iterates are those of the eager iteration, and the work
 // counts equal the oracle's (rbo_oracle.c newton_solve).  Result: x in U_NX, f returned.
-template <int D, int RPL, int HW>
+// NFIX: as evaluate's (the square full-wave layout's sites take it; the state machine's is run-time).
+template <int D, int RPL, int HW, int NFIX = -1>
 __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, int k, Counters& nevals,
                                          int& st, LaneRes<D, RPL, HW>& lr, double f0, bool have_f0, double gm0 = 0.0,
                                          double gs0 = 0.0, double sig0 = 0.0, double a0 = 0.0) {
@@ -1961,7 +1985,7 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
   wave_sync();
   // a batched start whose cheap certificate failed: the tight one at x_start (gμ, gσ, σ of the
   // batched value) before any gradient work
-  if (have_f0 && kp.gcert_sig > 0.0 && tight_certified<D, RPL, HW>(W, kp, S, gm0, gs0, sig0, 1.0 / sig0, a0)) {
+  if (have_f0 && kp.gcert_sig > 0.0 && tight_certified<D, RPL, HW, false, NFIX>(W, kp, S, gm0, gs0, sig0, 1.0 / sig0, a0)) {
     wave_sync();
     return f0;
   }
@@ -1988,18 +2012,18 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
     bool gradc;   // the gradient columns at x are still to run (the two-call loop, kp.newton_fused off)
     bool run = true;
     if (have_f0) {   // head of a batched run: GSTART + projected-gradient test + BACK
-      ran = evaluate<D, RPL, HW, EV_GSTART>(W, kp, S, EV_GSTART, lr, k, true);
+      ran = evaluate<D, RPL, HW, EV_GSTART, NFIX>(W, kp, S, EV_GSTART, lr, k, true);
       gradc = false;
     } else {         // head of a run without a batched start value: VALUE at the start point
       ns.trial = false;
-      ran = evaluate<D, RPL, HW, EV_VALUE>(W, kp, S, EV_VALUE, lr, k, false, &ns);
+      ran = evaluate<D, RPL, HW, EV_VALUE, NFIX>(W, kp, S, EV_VALUE, lr, k, false, &ns);
       ++nevals.value;
       run = (ns.why != NT_STOP);
       gradc = !(ran & EVR_GRAD);
     }
     while (run) {
       // the two-call loop: GRADC + projected-gradient test + BACK at x in a call of their own
-      if (gradc) ran = evaluate<D, RPL, HW, EV_GRADC>(W, kp, S, EV_GRADC, lr, k, true);
+      if (gradc) ran = evaluate<D, RPL, HW, EV_GRADC, NFIX>(W, kp, S, EV_GRADC, lr, k, true);
       ++nevals.grad;
       if (!(ran & EVR_BACK)) break;       // the projected-gradient test inside the evaluation: stationary
       ++nevals.hess;                      // the BACK part (Hα) ran in the same call: step
@@ -2013,7 +2037,7 @@ __device__ __forceinline__ double newton(WaveCtx<D, RPL, HW>& W, const KParams& 
       do {   // a backtrack repeats only the trial point and the VALUE call
         ns.dec = newton_trial_point<D, RPL, HW>(W, ns.t);
         STAMP(W, 14);
-        ran = evaluate<D, RPL, HW, EV_VALUE>(W, kp, S, EV_VALUE, lr, k, false, &ns);
+        ran = evaluate<D, RPL, HW, EV_VALUE, NFIX>(W, kp, S, EV_VALUE, lr, k, false, &ns);
         ++nevals.value;
       } while (ns.why == NT_BACKTRACK);
       if (ns.why == NT_STOP) break;
@@ -2156,8 +2180,9 @@ __device__ __forceinline__ void stage_start_tables(const KParams& kp, double* sm
 //   μ_k = c_S·kxb[:,k] + Σ_r c_r ψ(x_k, X_r),  Yf_r = E_r·kxb[:,k] + Σ_{q≤r} Dinv[r][q] ψ(x_k, X_q),
 //   σ_k² = ψ(0) − gtab[k][0] − Σ_r Yf_r²,  then α and the gradient certificate per lane.
 // Replaces nstarts value evaluations (and their wave-redundant EI) by one pass.
-template <int D, int RPL, int HW>
-__device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, double& f_lane,
+// NFIX: as evaluate's; the row loop's switch folds to its arm.
+template <int D, int RPL, int HW, int NFIX = -1>
+__device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, double& f_lane,
                                                    double& gm_lane, double& gs_lane, double& sig_lane,
                                                    double& a_lane, unsigned long long& stopmask,
                                                    unsigned long long& xnanmask, bool& varneg) {
@@ -2165,6 +2190,7 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
   constexpr int NR = Ly::NR;
   const double* U = W.U;
   const int lane = W.ln();
+  const int S = NFIX >= 0 ? NFIX - 1 : S_rt;
   const int ns = kp.nstarts, nf = S + 1;
   // ns ≤ 32: both half-waves take every start (lane k and k + 32); the lower half sums the
   // even data rows, the upper half the odd ones, one permlane32 swap per value adds the halves,
@@ -2271,7 +2297,8 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
     wave_sync();   // sums read before the scratch is reused
   } else {
     static_assert(FMAX == 4 || FMAX == 6, "batch_start_values: one row-loop copy per nf");
-    switch (nf) {
+    if constexpr (NFIX >= 0) sq_rows(std::integral_constant<int, NFIX>{});
+    else switch (nf) {
       case 0: sq_rows(std::integral_constant<int, 0>{}); break;   // base_solve: the base surface alone
       case 1: sq_rows(std::integral_constant<int, 1>{}); break;
       case 2: sq_rows(std::integral_constant<int, 2>{}); break;
@@ -2364,10 +2391,12 @@ __device__ __forceinline__ void batch_start_values(WaveCtx<D, RPL, HW>& W, const
 // multistart_base_solve!(fs, …) rbf_optim.jl:68-101 -> U[U_XB], over the starts k0 ≤ k < k1.
 // kp.base_solve: one start per launch item, whose (minimizer, minimum) is the output -- the
 // candidate list multistart_base_solve!(s::Surrogate, …) (:103-135) takes its findmin over.
-template <int D, int RPL, int HW>
-__device__ __forceinline__ int multistart(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S, Counters& nevals,
+// NFIX: as evaluate's, fixed for the whole multistart by the step's dispatch in trajectory().
+template <int D, int RPL, int HW, int NFIX = -1>
+__device__ __forceinline__ int multistart(WaveCtx<D, RPL, HW>& W, const KParams& kp, int S_rt, Counters& nevals,
                                           LaneRes<D, RPL, HW>& lr, int k0, int k1) {
   using Ly = Lay<D, RPL, HW>;
+  const int S = NFIX >= 0 ? NFIX - 1 : S_rt;
   double* U = W.U;
   const int lane = W.ln();
   int st = 0;
@@ -2388,7 +2417,7 @@ __device__ __forceinline__ int multistart(WaveCtx<D, RPL, HW>& W, const KParams&
   if (kp.batch) {
     bool varneg = false;
     STAMP(W, 16);
-    batch_start_values<D, RPL, HW>(W, kp, S, f_lane, gm_lane, gs_lane, sig_lane, a_lane, stopmask, xnanmask, varneg);
+    batch_start_values<D, RPL, HW, NFIX>(W, kp, S, f_lane, gm_lane, gs_lane, sig_lane, a_lane, stopmask, xnanmask, varneg);
     STAMP(W, 15);
     nevals.value += kp.nstarts;
     if (varneg) st |= 1;
@@ -2397,11 +2426,11 @@ __device__ __forceinline__ int multistart(WaveCtx<D, RPL, HW>& W, const KParams&
   // starts that need a Newton iteration, in index order (all of them without kp.batch)
   for (int k = k0; k < k1; ++k) {
     if ((stopmask >> k) & 1ull) continue;
-    const double fo = kp.batch ? newton<D, RPL, HW>(W, kp, S, k, nevals, st, lr, hw_lane_d<HW>(f_lane, k, W.half), true,
+    const double fo = kp.batch ? newton<D, RPL, HW, NFIX>(W, kp, S, k, nevals, st, lr, hw_lane_d<HW>(f_lane, k, W.half), true,
                                                 hw_lane_d<HW>(gm_lane, k, W.half), hw_lane_d<HW>(gs_lane, k, W.half),
                                                 hw_lane_d<HW>(sig_lane, k, W.half),
                                                 kp.cost ? hw_lane_d<HW>(a_lane, k, W.half) : 0.0)
-                               : newton<D, RPL, HW>(W, kp, S, k, nevals, st, lr, 0.0, false);
+                               : newton<D, RPL, HW, NFIX>(W, kp, S, k, nevals, st, lr, 0.0, false);
     if (kp.base_solve) {   // (Optim.minimizer(res), minimum(res)) of base_solve, rbf_optim.jl:127-128
       if (lane < D) kp.policy[(long long)k * D + lane] = U[Ly::U_NX + lane];
       if (lane == 0) kp.values[k] = fo;
@@ -2718,7 +2747,9 @@ __device__ __forceinline__ void restart_row_load(WaveCtx<D, RPL, HW>& W, const K
 // ================================================================================
 // One trajectory.
 // ================================================================================
-template <int D, int RPL, int HW>
+// STEPNF (the specialised kernel of the square full-wave layout): each step finds nf = S + 1 once
+// and runs its multistart in the copy of that nf (multistart<…, NFIX>).
+template <int D, int RPL, int HW, bool STEPNF = false>
 __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams& kp, long long tr) {
   using Ly = Lay<D, RPL, HW>;
   constexpr int D1 = Ly::D1, NR = Ly::NR;
@@ -2752,7 +2783,17 @@ __device__ __forceinline__ void trajectory(WaveCtx<D, RPL, HW>& W, const KParams
         if (lane < D) U[Ly::U_X + lane] = kp.replay[(long long)lane + D * ((k - 1) + (long long)h * (m + (long long)M * r))];
         wave_sync();
       } else {
+        // nf = S + 1 is found once per step; the multistart and every evaluation under it run the
+        // copy of that nf (base_solve: the nf = 0 arm)
+        if constexpr (STEPNF) {
+          static_assert(Ly::SQ && HW == 1, "trajectory: STEPNF is the square full-wave layout's");
+          nf_switch(S + 1, [&](auto nfc) {
+            st |= multistart<D, RPL, HW, decltype(nfc)::value>(W, kp, S, nevals, lr, bsolve ? (int)tr : 0,
+                                                               bsolve ? (int)tr + 1 : kp.nstarts);
+          });
+        } else {
         st |= multistart<D, RPL, HW>(W, kp, S, nevals, lr, bsolve ? (int)tr : 0, bsolve ? (int)tr + 1 : kp.nstarts);
+        }
         if (bsolve) {   // the start's minimizer and minimum were written by multistart
           if (lane == 0) kp.status[tr] = st & ~8;   // a NaN minimizer is the host's filter, not an error
           if (kp.evals && lane == 0) {
@@ -3153,6 +3194,14 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
   }
 }
 
+// The dimensions whose specialised square full-wave kernel fixes nf per step (trajectory's STEPNF):
+// d = 6, the benchmarked configuration's (C3), and d = 2 (C2 on the full-wave kernel), the second
+// dimension the tests hold to the parent's bits.  A kernel with the dispatch carries the Newton
+// path once per arm -- 2.7 to 3 times the code -- and with every d ≤ 8 and the generic kernel in,
+// the library's build took half as long again, so a further d is added where a
+// workload runs it.
+constexpr bool step_nf_dim(int d) { return d == 2 || d == 6; }
+
 template <int D, int RPL, int SPEC, int HW = 1>
 __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RPL, HW>::waves_per_simd)) rollout_kernel(KParams kp_in) {
   KParams kp = kp_in;   // a local copy: the fixed fields below propagate as constants
@@ -3207,7 +3256,9 @@ __global__ void __launch_bounds__((KBounds<D, RPL, HW>::threads), (KBounds<D, RP
 #ifdef MRBO_TAIL
     const unsigned long long t_tr = __builtin_amdgcn_s_memrealtime();
 #endif
-    trajectory<D, RPL, HW>(W, kp, tr);
+    // the per-step nf dispatch: the Matérn-5/2 + EI kernel of the square full-wave layout at the
+    // dimensions of step_nf_dim (the others and the generic kernel keep the run-time form)
+    trajectory<D, RPL, HW, Ly::SQ && HW == 1 && SPEC == 1 && step_nf_dim(D)>(W, kp, tr);
 #ifdef MRBO_TAIL
     ++n_taken;
     // per-trajectory wall time after the per-wave records (3 per wave of the grid)
