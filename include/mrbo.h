@@ -545,6 +545,38 @@ int mrbo_gp_optimize_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t
                                    double* theta, double* nll, double* grad, double* s2, int32_t* iters,
                                    int32_t* result, uint32_t flags, void* stream);
 
+/* ARD lengthscales (build-defined, no reference counterpart): θ = (ℓ_1 … ℓ_d), one lengthscale per
+ * input dimension, for Matérn-5/2, -3/2, -1/2 and SE.  These kernels see x only through
+ * ρ = ‖(x − x′)/ℓ‖, so the model is the unit-lengthscale GP on z = x/ℓ (componentwise):
+ *   K_ik = ψ(ρ_ik; ℓ = 1) + σn2·δ_ik,  ρ_ik = ‖z_i − z_k‖,
+ *   ∂K_ik/∂ℓ_u = g(ρ_ik)·(x_iu − x_ku)²/ℓ_u³,  g(ρ) = −ψ′(ρ; 1)/ρ  (0 on the diagonal and where ρ_ik = 0).
+ * s[q].lengthscale and s[q].period are ignored.
+ *
+ * mrbo_gp_fit_ard_multi: mrbo_gp_fit_multi's layouts with nt = d -- ells d×P×S (candidate p of data
+ * set q at ells[(p + q·P)·d ..]), ll P×S, grad d×P×S, status P×S, L_out N×N×P×S (zeros above the
+ * diagonal) and c_out N×P×S optional.  s2 = NULL: the plain likelihood, ll = −yᵀc/2 − Σ log L_ii −
+ * (N/2) log 2π and grad_u = (cᵀδK_u c − tr(K⁻¹δK_u))/2.  s2 (P×S) given: the profiled-amplitude
+ * likelihood of mrbo_gp_fit_profile_multi with the same δK_u, and s2 = yᵀc/N.
+ * status: 0 ok; 1 a pivot is not positive; 2 profile mode and yᵀc is not positive and finite;
+ * 3 some ℓ_u is not positive and finite (checked before K is built).  ll, grad and s2 are NaN on any
+ * non-zero status, and every other slot of the launch is as it would be without the failing one:
+ * block q carries the bits of the S = 1 call on data set q, candidate p those of a P = 1 call.
+ * Before any device call: mrbo_gp_fit_multi's checks on s, S and P; Periodic → MRBO_ERR_ARG;
+ * N > 128 or d > 16 → MRBO_ERR_UNSUPPORTED (one workgroup holds a candidate's z, factor, inverse and
+ * coefficients in LDS). */
+int mrbo_gp_fit_ard_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, const double* ells, double* ll,
+                          double* grad, double* s2, int32_t* status, double* L_out, double* c_out, uint32_t flags,
+                          void* stream);
+/* mrbo_gp_optimize_multi over the d lengthscales: ell0 d×S starts, lower and upper d each (HOST
+ * memory; non-finite or lower > upper → MRBO_ERR_ARG), ells and grad d×S, nll, iters S.  s2 = NULL
+ * minimises −ll, s2 (S) given −ll_p with ŝ² at the returned ells.  The step kernel performs
+ * mle.lbfgs_scalar's operations on d variables in its order (a dot product is a0·b0 + a1·b1 + …
+ * left to right, nothing fused), so the result is the specification's bit for bit. */
+int mrbo_gp_optimize_ard_multi(const mrbo_surrogate_t* s, int32_t S, const double* ell0, const double* lower,
+                               const double* upper, const mrbo_mle_opts_t* opts, double* ells, double* nll,
+                               double* grad, double* s2, int32_t* iters, int32_t* result, uint32_t flags,
+                               void* stream);
+
 /* Host helpers (HOST memory). */
 int mrbo_rnstream(int32_t M, int32_t d, int32_t H, double* out);                 /* M×(d+1)×H */
 int mrbo_initial_guesses(int32_t n, int32_t d, const double* lbs, const double* ubs, double* out); /* d×(n+2) */

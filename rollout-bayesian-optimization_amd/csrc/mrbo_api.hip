@@ -1615,7 +1615,7 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
 // once and launches every round of its minimisation.
 
 // the argument checks on s, S and nt, before the first HIP call (`multi` only words the messages)
-static int gp_fit_check(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, bool multi) {
+static int gp_fit_check(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, bool multi, bool ard = false) {
   if (ns < 1) return fail(MRBO_ERR_ARG, "gp_fit_multi: S=%d", ns);
   const int d = s->d, N = s->N;
   for (int q = 0; q < ns; ++q) {
@@ -1628,6 +1628,14 @@ static int gp_fit_check(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, bool 
   }
   if (N > 512) return fail(MRBO_ERR_UNSUPPORTED, "N=%d > 512", N);
   if (s->kernel < 0 || s->kernel > 4) return fail(MRBO_ERR_UNSUPPORTED, "gp_fit: kernel id %d", s->kernel);
+  if (ard) {   // θ = (ℓ_1 … ℓ_d): the radial kernels of one lengthscale, within the ARD kernel's LDS layout
+    if (s->kernel == 4) return fail(MRBO_ERR_ARG, "gp_fit_ard: the Periodic kernel has no ARD form");
+    if (N > GPFIT_ARD_NMAX || d > GPFIT_ARD_DMAX)
+      return fail(MRBO_ERR_UNSUPPORTED, "gp_fit_ard: d=%d N=%d: the ARD fit holds N <= %d and d <= %d", d, N,
+                  GPFIT_ARD_NMAX, GPFIT_ARD_DMAX);
+    if (ns > 65535) return fail(MRBO_ERR_UNSUPPORTED, "gp_fit_multi: S=%d > 65535 (the grid's second dimension)", ns);
+    return MRBO_OK;
+  }
   // θ = (ℓ) for the one-parameter kernels; Periodic takes (ℓ) (period fixed at s->period) or (ℓ, p)
   if (nt < 1 || nt > (s->kernel == 4 ? 2 : 1)) return fail(MRBO_ERR_ARG, "gp_fit: nt=%d for kernel %d", nt, s->kernel);
   if (s->kernel == 4 && nt == 1)
@@ -1645,6 +1653,7 @@ struct GpFitStaged {
   Pinned pin_in;
   size_t n_th, n_in;
   GpFitParams q{};   // the caller sets the outputs (L_out, c_out before gp_fit_stage: they select the kernel)
+  bool ard = false;  // the ARD fit (mrbo_gpfit_ard.hip): its LDS layout, no workspace
   GpFitStaged(size_t n_theta, size_t n_data) : pin_in(sizeof(double) * (n_theta + n_data)), n_th(n_theta), n_in(n_theta + n_data) {}
   // after an error: the buffers go back to the pool only when the stream has drained (a copy or
   // a kernel may still use them)
@@ -1679,12 +1688,12 @@ static int gp_fit_stage(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const
     int dev = 0, lds_max = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-    const size_t need = gpfit_launch_lds(q);
+    const size_t need = f.ard ? gpfit_ard_lds() : gpfit_launch_lds(q);
     if (need > (size_t)lds_max)
       return fail(MRBO_ERR_UNSUPPORTED, "gp_fit: d=%d N=%d needs %zu B of LDS per workgroup, the device has %d", d, N,
                   need, lds_max);
   }
-  if (!gpfit_in_regs(q) && !gpfit_in_lds(q)) {   // the register (N ≤ 64) and LDS (N ≤ 80) kernels need none
+  if (!f.ard && !gpfit_in_regs(q) && !gpfit_in_lds(q)) {   // the register (N ≤ 64) and LDS (N ≤ 80) kernels need none
     q.work = (double*)f.sg.slot(sizeof(double) * gpfit_tile_work_doubles(N, nt) * ncand);
     if (!q.work) return fail(MRBO_ERR_NOMEM, "gp_fit workspace");
   }
@@ -1709,7 +1718,8 @@ static int gp_fit_stage(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const
 
 // one launch of grid (P, S) on `st`, not synchronised
 static hipError_t gp_fit_launch(int P, int S, hipStream_t st, const GpFitParams& q, const GpFitMode& pm) {
-  launch_gpfit(P, S, st, q, pm);
+  if (pm.ard) launch_gpfit_ard(P, S, st, q, pm);
+  else launch_gpfit(P, S, st, q, pm);
   return hipGetLastError();
 }
 
@@ -1732,9 +1742,10 @@ static int gp_fit_copy_back(const GpFitParams& q, const void* h_, size_t PS, siz
 // (s2: P×S, profile mode only)
 static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_t nt, const double* thetas, double* ll,
                        double* grad, double* s2, int32_t* status, double* L_out, double* c_out, uint32_t flags,
-                       void* stream, bool multi, bool profile) {
+                       void* stream, bool multi, bool profile, bool ard = false) {
   if (!s || !thetas || !ll || !grad || !status || np < 1 || (profile && !s2)) return fail(MRBO_ERR_ARG, "null argument");
-  if (const int rc = gp_fit_check(s, ns, nt, multi)) return rc;
+  if (const int rc = gp_fit_check(s, ns, nt, multi, ard)) return rc;
+  if (ard) nt = s->d;
   const int d = s->d, N = s->N;
   hipStream_t st = (hipStream_t)stream;
   const size_t S = (size_t)ns, PS = (size_t)np * S, NN = (size_t)N * N, NTP = (size_t)nt * PS, DN = (size_t)d * N;
@@ -1744,7 +1755,8 @@ static int gp_fit_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t np, int32_
   GpFitStaged f(host ? NTP : 0, DN * S + N * S + S);
   GpFitParams& q = f.q;
   const size_t out_bytes = sizeof(double) * (PS + NTP + (profile ? PS : 0)) + sizeof(int32_t) * PS;
-  GpFitMode pm{profile ? 1 : 0, profile ? s2 : nullptr};
+  GpFitMode pm{profile ? 1 : 0, profile ? s2 : nullptr, ard ? 1 : 0};
+  f.ard = ard;
   q.thetas = thetas;
   q.ll = ll;
   q.grad = grad;
@@ -1826,6 +1838,11 @@ int mrbo_gp_fit_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, i
   return gp_fit_impl(s, S, P, nt, thetas, ll, grad, s2, status, L_out, c_out, flags, stream, true, true);
 }
 
+int mrbo_gp_fit_ard_multi(const mrbo_surrogate_t* s, int32_t S, int32_t P, const double* ells, double* ll, double* grad,
+                          double* s2, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
+  return gp_fit_impl(s, S, P, 0, ells, ll, grad, s2, status, L_out, c_out, flags, stream, true, s2 != nullptr, true);
+}
+
 int mrbo_gp_fit_theta(const mrbo_surrogate_t* s, int32_t np, int32_t nt, const double* thetas, double* ll,
                       double* grad, int32_t* status, double* L_out, double* c_out, uint32_t flags, void* stream) {
   return gp_fit_impl(s, 1, np, nt, thetas, ll, grad, nullptr, status, L_out, c_out, flags, stream, false, false);
@@ -1881,11 +1898,12 @@ struct CheckEvents {
 static int gp_optimize_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, const double* theta0,
                             const double* lower, const double* upper, const mrbo_mle_opts_t* o, double* theta,
                             double* nll, double* grad, double* s2, int32_t* iters, int32_t* result, uint32_t flags,
-                            void* stream, bool profile) {
+                            void* stream, bool profile, bool ard = false) {
   // every argument check comes before the first HIP call
   if (!s || !theta0 || !lower || !upper || !theta || !nll || !grad || !iters || !result || (profile && !s2))
     return fail(MRBO_ERR_ARG, "gp_optimize_multi: null argument");
-  if (const int rc = gp_fit_check(s, ns, nt, true)) return rc;
+  if (const int rc = gp_fit_check(s, ns, nt, true, ard)) return rc;
+  if (ard) nt = s->d;
   MleParams mp{};
   for (int t = 0; t < nt; ++t) {
     if (!std::isfinite(lower[t]) || !std::isfinite(upper[t]) || lower[t] > upper[t])
@@ -1940,7 +1958,8 @@ static int gp_optimize_impl(const mrbo_surrogate_t* s, int32_t ns, int32_t nt, c
   mp.hs = dgll + NT * P;
   mp.hy = mp.hs + NT * M;
   mp.al = mp.hy + NT * M;
-  GpFitMode pm{profile ? 1 : 0, profile ? mp.al + M * S : nullptr};
+  GpFitMode pm{profile ? 1 : 0, profile ? mp.al + M * S : nullptr, ard ? 1 : 0};
+  f.ard = ard;
   int* dst = (int*)(mp.al + M * S + P * S2);
   mp.ring = dst + P * S;
   mp.check = mp.ring + 3 * S;
@@ -2038,6 +2057,13 @@ int mrbo_gp_optimize_profile_multi(const mrbo_surrogate_t* s, int32_t S, int32_t
                                    double* nll, double* grad, double* s2, int32_t* iters, int32_t* result,
                                    uint32_t flags, void* stream) {
   return gp_optimize_impl(s, S, nt, theta0, lower, upper, o, theta, nll, grad, s2, iters, result, flags, stream, true);
+}
+
+int mrbo_gp_optimize_ard_multi(const mrbo_surrogate_t* s, int32_t S, const double* ell0, const double* lower,
+                               const double* upper, const mrbo_mle_opts_t* o, double* ells, double* nll, double* grad,
+                               double* s2, int32_t* iters, int32_t* result, uint32_t flags, void* stream) {
+  return gp_optimize_impl(s, S, 0, ell0, lower, upper, o, ells, nll, grad, s2, iters, result, flags, stream,
+                          s2 != nullptr, true);
 }
 
 int mrbo_plan_set_order(mrbo_plan_t* P, const int32_t* order, int64_t n) {

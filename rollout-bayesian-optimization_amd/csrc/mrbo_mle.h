@@ -1,6 +1,6 @@
 // mrbo_mle.h -- interface between the host API (mrbo_api.hip) and the step kernel of
 // mrbo_gp_optimize_multi (mrbo_mle.hip): the projected L-BFGS between two fit launches, S
-// independent problems over nt ≤ 2 hyperparameters, one thread each.  The fit launches
+// independent problems over nt ≤ 16 hyperparameters, one thread each.  The fit launches
 // (mrbo_gpfit.hip) read `trial` (the start launch: `x`) and write ll, gll, status; the rest is the
 // minimiser's own state.
 #pragma once
@@ -10,7 +10,7 @@ namespace mrbo {
 
 constexpr int MLE_STEPS = 12;      // trial steps of one line search: 1, 1/2, ..., 2⁻¹¹ (mle.py _STEPS)
 constexpr int MLE_HIST_MAX = 16;   // L-BFGS pairs kept, at most
-constexpr int MLE_NT_MAX = 2;
+constexpr int MLE_NT_MAX = 16;     // 1 (ℓ), 2 (ℓ, p: Periodic), or d ≤ 16 lengthscales (the ARD refit)
 
 struct MleParams {
   int S, nt, m, iterations;        // m: pairs kept

@@ -2,11 +2,11 @@
 // projected L-BFGS does between two evaluations, so that the S minimisations of −log_likelihood
 // advance from fit launch to fit launch without a host round trip.
 //
-// One thread per problem (the work is a few hundred scalar operations on nt ≤ 2 variables; the
+// One thread per problem (the work is a few hundred scalar operations on nt ≤ 16 variables; the
 // fit launches between two steps are the time).  The specification is mle.py lbfgs_scalar: every
 // operation below is the one there, in its order, in fp64, each rounded on its own -- no fused
 // multiply-add (contraction is off for this unit), plain division and square root, a dot product
-// as a0*b0 + a1*b1.  The results are therefore the specification's bit for bit
+// as a0*b0 + a1*b1 + ... left to right.  The results are therefore the specification's bit for bit
 // (tests/test_gpu_mle_device.py).  The iterate, its objective, gradient and iteration count live
 // in the call's output arrays; the (s, y) pairs and the recursion's α in global memory, so no
 // array is indexed at run time in registers and the kernel needs no scratch.
@@ -253,10 +253,16 @@ void launch_mle_init(hipStream_t st, const MleParams& p) {
 
 void launch_mle_step(bool first, int slot, hipStream_t st, const MleParams& p) {
   const dim3 block(p.S <= 64 ? 64 : 256);
-  if (p.nt == 1)
-    hipLaunchKernelGGL(mle_step_kernel<1>, dim3(1), block, 0, st, p, first ? 1 : 0, slot);
-  else
-    hipLaunchKernelGGL(mle_step_kernel<2>, dim3(1), block, 0, st, p, first ? 1 : 0, slot);
+  // nt = 1, 2: ℓ and (ℓ, p); 3..16: the ARD refit's d lengthscales (mrbo_gp_optimize_ard_multi)
+#define MRBO_MLE_STEP(NT) \
+  case NT: hipLaunchKernelGGL(mle_step_kernel<NT>, dim3(1), block, 0, st, p, first ? 1 : 0, slot); break;
+  switch (p.nt) {
+    MRBO_MLE_STEP(1) MRBO_MLE_STEP(2) MRBO_MLE_STEP(3) MRBO_MLE_STEP(4) MRBO_MLE_STEP(5) MRBO_MLE_STEP(6)
+    MRBO_MLE_STEP(7) MRBO_MLE_STEP(8) MRBO_MLE_STEP(9) MRBO_MLE_STEP(10) MRBO_MLE_STEP(11) MRBO_MLE_STEP(12)
+    MRBO_MLE_STEP(13) MRBO_MLE_STEP(14) MRBO_MLE_STEP(15) MRBO_MLE_STEP(16)
+    default: break;   // the host API admits nt ≤ MLE_NT_MAX only
+  }
+#undef MRBO_MLE_STEP
 }
 
 }  // namespace mrbo

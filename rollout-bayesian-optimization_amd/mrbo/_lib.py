@@ -40,6 +40,7 @@ EXPORTS = [
     "mrbo_box_adam_step", "mrbo_pick_restart", "mrbo_rollout_solve",
     "mrbo_simulate_control", "mrbo_eto_reduce_cv", "mrbo_plan_set_control_variate",
     "mrbo_gp_fit_profile_multi", "mrbo_gp_optimize_profile_multi",
+    "mrbo_gp_fit_ard_multi", "mrbo_gp_optimize_ard_multi",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM, MRBO_OPT_BOX_ADAM = 0, 1, 2
@@ -147,6 +148,11 @@ def load():
     L.mrbo_gp_optimize_profile_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, _vp,
                                                  _vp, _vp, ctypes.POINTER(MleOpts), _vp, _vp, _vp, _vp, _vp,
                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
+    L.mrbo_gp_fit_ard_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]
+    L.mrbo_gp_optimize_ard_multi.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, _vp, _vp, _vp,
+                                             ctypes.POINTER(MleOpts), _vp, _vp, _vp, _vp, _vp,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, _vp]
     L.mrbo_last_kernel_ms.argtypes = [_vp]
     L.mrbo_last_kernel_ms.restype = ctypes.c_double
     L.mrbo_plan_info.argtypes = [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]

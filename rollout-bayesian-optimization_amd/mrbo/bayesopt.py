@@ -238,12 +238,48 @@ def _check_parallel_trials(parallel_trials, reuse_surrogate):
     return k
 
 
+# ---- ARD surrogates in the loops (build-defined) ------------------------------
+ARD_LB, ARD_UB = 0.1, 5.0            # the refit's box in every dimension: [0.1, 5]^d, as KERNEL_LBS / KERNEL_UBS
+
+
+def _new_surrogate(ard, X, y, capacity, rule, standardize):
+    """The loops' surrogate: Matérn-5/2, σn2 = 1e-6; with `ard` an ARDSurrogate starting at ℓ_u = 1."""
+    if ard:
+        from .ard import ARDSurrogate
+        return ARDSurrogate(Matern52(), X, y, capacity=capacity, decision_rule=rule, σn2=1e-6, standardize=standardize)
+    return Surrogate(Matern52(), X, y, capacity=capacity, decision_rule=rule, σn2=1e-6, standardize=standardize)
+
+
+def _ard_rollout_pick(s, lbs, ubs, *args, **kw):
+    """rollout_solve on ARDSurrogate s: the solve runs on s.inner over the whitened box, xnext is mapped
+    back and clipped to the raw box.  The solver's step `eta` therefore acts in whitened coordinates
+    (units of the fitted lengthscale; BoxAdam: widths of the whitened box)."""
+    zl, zu = s.whitened_box(lbs, ubs)
+    znext, mean = rollout_solve(s.inner, zl, zu, *args, **kw)
+    return np.clip(s.unwhiten(znext), lbs, ubs), mean
+
+
+def _ard_myopic_pick(s, lbs, ubs, guesses, theta, device):
+    """multistart_base_solve on ARDSurrogate s: guesses and box whitened, the solve on s.inner (its
+    x_tol acts in whitened coordinates), the minimiser mapped back and clipped to the raw box."""
+    from .rbf_optim import base_solve_batch, findmin_candidates
+    zl, zu = s.whitened_box(lbs, ubs)
+    zs, fs, _ = base_solve_batch(s.inner, zl, zu, s.whiten(guesses), [theta], device=device)
+    return np.clip(s.unwhiten(zs[:, findmin_candidates(zs, fs)]), lbs, ubs)
+
+
+def _check_ard(ard, optimize):
+    if ard and not optimize:
+        raise ValueError("ard=True needs optimize=True: the ARD lengthscales are what the refit fits "
+                         "(without it every ℓ_u stays 1, the isotropic default)")
+
+
 # ---- the experiment loop (nonmyopic_bayesopt.jl:120-300) -------------------------------------
 def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, mc_samples=200, batch_size=8,
         sgd_iterations=50, optimize=False, seed=1906, device=0, log=print, rules=("ei", "poi", "lcb"), eta=0.01,
         initial_observations=INITIAL_OBSERVATIONS, solver="sga", fmini_over_capacity=True, incumbent=True,
         reuse_surrogate=True, parallel_trials=1, device_mle=False, device_solve=False, variance_reduction=False,
-        standardize=False):
+        standardize=False, ard=False):
     """The experiment loop; `rules` selects a subset of the reference's three acquisitions (all by
     default, as nonmyopic_bayesopt.jl), `eta` the StandardSGA step of the build-defined solver
     (default 0.01, StandardSGA's own default, optimizers.jl:9),
@@ -270,8 +306,16 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     standardize=True (build-defined): the surrogates fit their output scale
     (Surrogate(standardize=True): y = m + s·g), the acquisition runs on the standardised
     observations and `optimize` maximises the profiled-amplitude likelihood.  Gaps, regrets, minimum
-    observations and the returned y stay in the objective's raw units."""
+    observations and the returned y stay in the objective's raw units.
+    ard=True (build-defined; needs optimize=True, else ValueError): ARDSurrogates, one
+    lengthscale per input dimension.  Each step refits the ells in the box [0.1, 5]^d (on the host, or with
+    device_mle as one device call; with parallel_trials > 1 one batched refit per chunk), runs the
+    acquisition solve on the surrogate's `inner` over the whitened box z = x/ells, maps xnext back and clips
+    it to the raw box.  The inner solve's x_tol and the outer ascent's `eta` therefore act in whitened
+    coordinates, i.e. in units of the fitted lengthscales.  Lockstep trials solve one trial at a time
+    (their whitened boxes differ).  Every result carries `ells`, the trial's final lengthscales."""
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
+    _check_ard(ard, optimize)
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
     directory = os.path.join(output_dir, function_name)
@@ -291,17 +335,16 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     results = {}
     sur = None
     if reuse_surrogate:    # :233 "Preallocate entire surrogate object and reuse"
-        sur = Surrogate(Matern52(), np.zeros((testfn.dim, 1)), np.zeros(1), capacity=budget + initial_observations,
-                        σn2=1e-6, standardize=standardize)
+        sur = _new_surrogate(ard, np.zeros((testfn.dim, 1)), np.zeros(1), budget + initial_observations, None,
+                             standardize)
     for acq, rule, theta in zip(acquisitions, rules, dr_hypers):
         if reuse_surrogate:
             sur.set_decision_rule(rule)                                   # :241
         log(f"Conducting experiments with acquisition = {acq}")
         for t0_ in range(0, trials if parallel_trials > 1 else 0, parallel_trials):
             chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
-            surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
-                              capacity=budget + initial_observations, decision_rule=rule, σn2=1e-6,
-                              standardize=standardize) for t in chunk]
+            surs = [_new_surrogate(ard, initial_samples[t], testfn(initial_samples[t]), budget + initial_observations,
+                                   rule, standardize) for t in chunk]
             for s in surs:
                 s.fmini_over_capacity = fmini_over_capacity
             ell_starts = [float(s.ψ.lengthscale) for s in surs]
@@ -310,9 +353,16 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
             mle_times = np.zeros(budget)   # wall time of the chunk's batched refit per budget step
             for b in range(budget):
                 t0 = time.perf_counter()
-                picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
-                                            theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
-                                            device_solve=device_solve, variance_reduction=variance_reduction)
+                if ard:   # the trials' whitened boxes differ: one solve per trial
+                    picks = [_ard_rollout_pick(s, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
+                                               theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
+                                               device_solve=device_solve, variance_reduction=variance_reduction)
+                             for s in surs]
+                else:
+                    picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts,
+                                                sgd_iterations, theta, eta=eta, device=device, solver=solver,
+                                                incumbent=incumbent, device_solve=device_solve,
+                                                variance_reduction=variance_reduction)
                 dt = time.perf_counter() - t0
                 for s, r, (xnext, _), initial_best in zip(surs, rec, picks, initial_bests):
                     r["times"][b] = dt
@@ -324,7 +374,11 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                 if optimize:   # every trial has conditioned: one batched refit for the chunk
                     from .mle import optimize_multi
                     t0 = time.perf_counter()
-                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
+                    if ard:
+                        from .ard import optimize_ard_multi
+                        optimize_ard_multi(surs, ARD_LB, ARD_UB, device=device_mle)
+                    else:
+                        optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                     mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start in zip(chunk, surs, rec, ell_starts):
                 log(f"{acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, {r['times'].sum():.2f} s of solves")
@@ -335,14 +389,15 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
                                              X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
                                              ell_start=ell_start, ell_end=float(s.ψ.lengthscale),
                                              repeats=np.zeros(budget, dtype=bool))
+                if ard:
+                    results[(acq, trial)]["ells"] = s.ells.copy()
         for trial in range(trials if parallel_trials == 1 else 0):
             Xinit = initial_samples[trial]
             yinit = testfn(Xinit)
             if reuse_surrogate:
                 sur.reset(Xinit, yinit)                                   # :253
             else:
-                sur = Surrogate(Matern52(), Xinit, yinit, capacity=budget + initial_observations, decision_rule=rule,
-                                σn2=1e-6, standardize=standardize)
+                sur = _new_surrogate(ard, Xinit, yinit, budget + initial_observations, rule, standardize)
             sur.fmini_over_capacity = fmini_over_capacity
             ell_start = float(sur.ψ.lengthscale)
             initial_best = float(np.min(yinit))
@@ -350,15 +405,19 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
             repeats = np.zeros(budget, dtype=bool)
             for b in range(budget):
                 t0 = time.perf_counter()
-                xnext, _ = rollout_solve(sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
-                                         theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
-                                         device_solve=device_solve, variance_reduction=variance_reduction)
+                xnext, _ = (_ard_rollout_pick if ard else rollout_solve)(
+                    sur, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta, eta=eta,
+                    device=device, solver=solver, incumbent=incumbent, device_solve=device_solve,
+                    variance_reduction=variance_reduction)
                 times[b] = time.perf_counter() - t0
                 observed_best = float(np.min(sur.get_active_observations()))
                 regrets[b] = simple_regret(true_minimum, observed_best)
                 gaps[b] = gap(initial_best, observed_best, true_minimum)
                 sur.condition(xnext, float(testfn.f(xnext)))
-                if optimize:
+                if optimize and ard:
+                    from .ard import optimize_ard
+                    optimize_ard(sur, ARD_LB, ARD_UB, device=device_mle)
+                elif optimize:
                     from .mle import optimize as mle_optimize
                     mle_optimize(sur, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                 minobs[b] = float(np.min(sur.get_active_observations()))
@@ -368,6 +427,8 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
             results[(acq, trial)] = dict(times=times, gaps=gaps, simple_regret=regrets, minimum_observations=minobs,
                                          X=sur.get_active_covariates().copy(), y=sur.get_active_observations().copy(),
                                          ell_start=ell_start, ell_end=float(sur.ψ.lengthscale), repeats=repeats)
+            if ard:
+                results[(acq, trial)]["ells"] = sur.ells.copy()
     return results
 
 
@@ -378,7 +439,7 @@ MYOPIC_RULES = {"ei": (EI, 0.0), "poi": (POI, 0.0), "lcb": (LCB, 2.0)}   # :151-
 def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed=1906, device=0, log=print,
                rules=("ei", "poi", "lcb"), optimize=True, initial_observations=INITIAL_OBSERVATIONS,
                reuse_surrogate=True, capacity=None, solve_margin=0.0, no_repeat=False, parallel_trials=1,
-               device_mle=False, standardize=False):
+               device_mle=False, standardize=False, ard=False):
     """myopic_bayesopt.jl's loop: per budget step xnext = multistart_base_solve!(sur, …; guesses =
     generate_initial_guesses(starts, lbs, ubs), θfixed) -- the deterministic multistart local solve of
     the analytic acquisition on the base surrogate (:224-233), here mrbo_base_solve on the device --
@@ -403,9 +464,16 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     lockstep, every budget step one mrbo_base_solve launch on their k surrogates (base_solve_multi).
     device_mle=True: optimize!'s minimisation runs as one device-resident call
     (mle.optimize(..., device=True)); the default keeps the host-driven loop.
-    standardize=True: surrogates that fit their output scale, as in run."""
+    standardize=True: surrogates that fit their output scale, as in run.
+    ard=True (needs optimize=True, else ValueError; not with the no_repeat diagnostic): ARDSurrogates as in
+    run -- the ells refit in [0.1, 5]^d after every observation, the multistart solve on `inner` with the
+    guesses and the box whitened (its x_tol in whitened coordinates, units of the fitted lengthscales),
+    the minimiser mapped back and clipped to the raw box; lockstep trials solve one trial at a time."""
     from .rbf_optim import base_solve_batch, base_solve_multi, findmin_candidates, multistart_base_solve
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
+    _check_ard(ard, optimize)
+    if ard and no_repeat:
+        raise ValueError("ard=True: the no_repeat diagnostic is not available on ARD surrogates")
     from .utils import generate_initial_guesses
     testfn = TESTFNS[function_name]()
     lbs, ubs = testfn.get_bounds()
@@ -425,8 +493,8 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     if reuse_surrogate:    # :205 "Preallocate entire surrogate object and reuse"
         # capacity = BUDGET as the reference; it must hold the initial design (a reset! past
         # capacity is a BoundsError in Julia), so a budget below it gets the design's size
-        sur = Surrogate(Matern52(), np.zeros((testfn.dim, 1)), np.zeros(1),
-                        capacity=capacity or max(budget, initial_observations), σn2=1e-6, standardize=standardize)
+        sur = _new_surrogate(ard, np.zeros((testfn.dim, 1)), np.zeros(1),
+                             capacity or max(budget, initial_observations), None, standardize)
     for acq in rules:
         make_rule, theta = MYOPIC_RULES[acq]
         if reuse_surrogate:
@@ -434,9 +502,9 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
         log(f"Conducting experiments with acquisition = {acq}")
         for t0_ in range(0, trials if parallel_trials > 1 else 0, parallel_trials):
             chunk = list(range(t0_, min(t0_ + parallel_trials, trials)))
-            surs = [Surrogate(Matern52(), initial_samples[t], testfn(initial_samples[t]),
-                              capacity=capacity or budget + initial_observations, decision_rule=make_rule(),
-                              σn2=1e-6, standardize=standardize) for t in chunk]
+            surs = [_new_surrogate(ard, initial_samples[t], testfn(initial_samples[t]),
+                                   capacity or budget + initial_observations, make_rule(), standardize)
+                    for t in chunk]
             ell_starts = [float(s.ψ.lengthscale) for s in surs]
             initial_bests = [float(np.min(testfn(initial_samples[t]))) for t in chunk]
             rec = [{m: np.zeros(budget) for m in METRICS} for _ in chunk]
@@ -446,15 +514,21 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             for b in range(budget):
                 t0 = time.perf_counter()
                 w = (ubs - lbs) * solve_margin
-                xs_, fs_, _ = base_solve_multi(surs, lbs + w, ubs - w, guesses, [theta], device=device)
+                if ard:   # the trials' whitened boxes differ: one solve per trial
+                    ard_next = [_ard_myopic_pick(s, lbs + w, ubs - w, guesses, theta, device) for s in surs]
+                else:
+                    xs_, fs_, _ = base_solve_multi(surs, lbs + w, ubs - w, guesses, [theta], device=device)
                 dt = time.perf_counter() - t0
                 for q, (s, r, initial_best) in enumerate(zip(surs, rec, initial_bests)):
-                    xq, fq = xs_[:, :, q], fs_[:, q]
                     Xo = s.X[:, :s.observed]
-                    fresh = [i for i in range(xq.shape[1])
-                             if not (np.abs(Xo - xq[:, i:i + 1]) <= tol).all(axis=0).any()] if no_repeat else []
-                    xnext = (xq[:, fresh[findmin_candidates(xq[:, fresh], fq[fresh])]] if fresh
-                             else xq[:, findmin_candidates(xq, fq)]).copy()
+                    if ard:
+                        xnext = ard_next[q]
+                    else:
+                        xq, fq = xs_[:, :, q], fs_[:, q]
+                        fresh = [i for i in range(xq.shape[1])
+                                 if not (np.abs(Xo - xq[:, i:i + 1]) <= tol).all(axis=0).any()] if no_repeat else []
+                        xnext = (xq[:, fresh[findmin_candidates(xq[:, fresh], fq[fresh])]] if fresh
+                                 else xq[:, findmin_candidates(xq, fq)]).copy()
                     r["times"][b] = dt
                     reps[q][b] = bool((np.abs(Xo - xnext[:, None]) <= tol).all(axis=0).any())
                     observed_best = float(np.min(s.get_active_observations()))
@@ -465,7 +539,11 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                 if optimize:   # every trial has conditioned: one batched refit for the chunk
                     from .mle import optimize_multi
                     t0 = time.perf_counter()
-                    optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
+                    if ard:
+                        from .ard import optimize_ard_multi
+                        optimize_ard_multi(surs, ARD_LB, ARD_UB, device=device_mle)
+                    else:
+                        optimize_multi(surs, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                     mle_times[b] = time.perf_counter() - t0
             for trial, s, r, ell_start, rp in zip(chunk, surs, rec, ell_starts, reps):
                 log(f"myopic {acq} trial {trial + 1}/{trials}: gap {r['gaps'][-1]:.4f}, "
@@ -476,14 +554,16 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                                              minimum_observations=r["minimum_observations"], mle_times=mle_times.copy(),
                                              X=s.get_active_covariates().copy(), y=s.get_active_observations().copy(),
                                              ell_start=ell_start, ell_end=float(s.ψ.lengthscale), repeats=rp)
+                if ard:
+                    results[(acq, trial)]["ells"] = s.ells.copy()
         for trial in range(trials if parallel_trials == 1 else 0):
             Xinit = initial_samples[trial]
             yinit = testfn(Xinit)
             if reuse_surrogate:
                 sur.reset(Xinit, yinit)                                   # :217
             else:
-                sur = Surrogate(Matern52(), Xinit, yinit, capacity=capacity or budget + initial_observations,
-                                decision_rule=make_rule(), σn2=1e-6, standardize=standardize)
+                sur = _new_surrogate(ard, Xinit, yinit, capacity or budget + initial_observations, make_rule(),
+                                     standardize)
             ell_start = float(sur.ψ.lengthscale)
             initial_best = float(np.min(yinit))
             times, gaps, allocs, regrets, minobs = (np.zeros(budget) for _ in range(5))
@@ -492,7 +572,9 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             for b in range(budget):
                 t0 = time.perf_counter()
                 w = (ubs - lbs) * solve_margin
-                if no_repeat:
+                if ard:
+                    xnext[:] = _ard_myopic_pick(sur, lbs + w, ubs - w, guesses, theta, device)
+                elif no_repeat:
                     xs_, fs_, _ = base_solve_batch(sur, lbs + w, ubs - w, guesses, [theta], device=device)
                     Xo = sur.X[:, :sur.observed]
                     tol = 1e-6 * (ubs - lbs)[:, None]
@@ -511,7 +593,10 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
                 regrets[b] = simple_regret(true_minimum, observed_best)
                 gaps[b] = gap(initial_best, observed_best, true_minimum)
                 sur.condition(xnext, float(testfn.f(xnext)))
-                if optimize:
+                if optimize and ard:
+                    from .ard import optimize_ard
+                    optimize_ard(sur, ARD_LB, ARD_UB, device=device_mle)
+                elif optimize:
                     from .mle import optimize as mle_optimize
                     mle_optimize(sur, KERNEL_LBS, KERNEL_UBS, device=device_mle)
                 minobs[b] = float(np.min(sur.get_active_observations()))
@@ -521,6 +606,8 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             results[(acq, trial)] = dict(times=times, gaps=gaps, simple_regret=regrets, minimum_observations=minobs,
                                          X=sur.get_active_covariates().copy(), y=sur.get_active_observations().copy(),
                                          ell_start=ell_start, ell_end=float(sur.ψ.lengthscale), repeats=repeats)
+            if ard:
+                results[(acq, trial)]["ells"] = sur.ells.copy()
     return results
 
 
@@ -550,6 +637,9 @@ def parse(argv=None):
     ap.add_argument("--standardize", action="store_true",
                     help="fit the surrogate's output scale (mean and amplitude) and run the acquisition on the "
                          "standardised observations; with --optimize the profiled-amplitude likelihood")
+    ap.add_argument("--ard", action="store_true",
+                    help="with --optimize: one lengthscale per input dimension (ARD), refit in [0.1, 5]^d; the "
+                         "acquisition solve runs in the whitened coordinates x/ell")
     return ap.parse_args(argv)
 
 
@@ -559,7 +649,7 @@ def main(argv=None):
         mc_samples=a.mc_samples, batch_size=a.batch_size, sgd_iterations=a.sgd_iterations, optimize=a.optimize,
         seed=a.seed, parallel_trials=a.parallel_trials, reuse_surrogate=a.parallel_trials == 1,
         device_mle=a.device_mle, device_solve=a.device_solve, variance_reduction=a.variance_reduction,
-        standardize=a.standardize)
+        standardize=a.standardize, ard=a.ard)
 
 
 if __name__ == "__main__":

@@ -294,15 +294,10 @@ def projected_lbfgs_multi(fg_multi, x0s, lower, upper, iterations=30, g_tol=1e-8
     return out
 
 
-def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1=1e-4):
-    """projected_lbfgs restated on Python floats: every operation of _lbfgs_problem written out
-    one rounding at a time -- a dot product is a0*b0 + a1*b1 + ... left to right, a norm the square
-    root of that, nothing fused.  This is the specification of the device minimiser
-    (mrbo_gp_optimize_multi's step kernel, csrc/mrbo_mle.hip, performs these operations in this
-    order in fp64), so the two agree bit for bit on the same evaluations.  For one variable it
-    equals projected_lbfgs exactly (a dot product is one multiplication); for more, numpy's `@` may
-    fuse its multiply-adds and the two can differ in the last bits.  Returns (x, f, g, iterations)
-    with x and g as arrays."""
+def _lbfgs_scalar_problem(x0, lower, upper, iterations, g_tol, m, c1):
+    """lbfgs_scalar as a coroutine with _lbfgs_problem's protocol: it yields the (P, n) points it needs
+    evaluated, is sent (f (P,), g (P, n)) for them, and returns (x, f, g, iterations).  lbfgs_scalar and
+    lbfgs_scalar_multi drive this one implementation."""
     lo = [float(v) for v in np.asarray(lower, float).ravel()]
     hi = [float(v) for v in np.asarray(upper, float).ravel()]
     n = len(lo)
@@ -329,12 +324,15 @@ def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1
                 r = v
         return r
 
-    def evaluate(points):
-        f, g = fg_batch(np.array(points, dtype=np.float64).reshape(len(points), n))
-        return [float(v) for v in f], [[float(v) for v in row] for row in np.asarray(g).reshape(len(points), n)]
+    def points(pts):
+        return np.array(pts, dtype=np.float64).reshape(len(pts), n)
+
+    def values(fg, npts):
+        f, g = fg
+        return [float(v) for v in f], [[float(v) for v in row] for row in np.asarray(g).reshape(npts, n)]
 
     x = [clip(float(v), i) for i, v in enumerate(np.asarray(x0, float).ravel())]
-    ft, gt = evaluate([x])
+    ft, gt = values((yield points([x])), 1)
     f, g = ft[0], gt[0]
     S, Y = [], []
     it = 0
@@ -366,7 +364,7 @@ def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1
         if dot(g, p) >= 0:                        # not a descent direction: steepest descent
             p = [-(g[i] if free[i] else 0.0) for i in R]
         trial = [[clip(x[i] + float(st) * p[i], i) for i in R] for st in _STEPS]
-        ft, gt = evaluate(trial)
+        ft, gt = values((yield points(trial)), len(trial))
         k = -1
         for kk in range(len(trial)):
             d = [trial[kk][i] - x[i] for i in R]
@@ -392,6 +390,45 @@ def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1
         if moved == 0.0:
             break
     return np.array(x), f, np.array(g), it
+
+
+def lbfgs_scalar(fg_batch, x0, lower, upper, iterations=30, g_tol=1e-8, m=10, c1=1e-4):
+    """projected_lbfgs restated on Python floats: every operation of _lbfgs_problem written out
+    one rounding at a time -- a dot product is a0*b0 + a1*b1 + ... left to right, a norm the square
+    root of that, nothing fused.  This is the specification of the device minimiser
+    (mrbo_gp_optimize_multi's step kernel, csrc/mrbo_mle.hip, performs these operations in this
+    order in fp64), so the two agree bit for bit on the same evaluations.  For one variable it
+    equals projected_lbfgs exactly (a dot product is one multiplication); for more, numpy's `@` may
+    fuse its multiply-adds and the two can differ in the last bits.  Returns (x, f, g, iterations)
+    with x and g as arrays."""
+    prob = _lbfgs_scalar_problem(x0, lower, upper, iterations, g_tol, m, c1)
+    pts = next(prob)
+    try:
+        while True:
+            pts = prob.send(fg_batch(pts))
+    except StopIteration as done:
+        return done.value
+
+
+def lbfgs_scalar_multi(fg_multi, x0s, lower, upper, iterations=30, g_tol=1e-8, m=10, c1=1e-4):
+    """lbfgs_scalar for one independent minimisation per row of x0s, in lockstep, with
+    projected_lbfgs_multi's protocol: fg_multi(idx, X) evaluates the pending points X (len(idx), P, n) of
+    the problems still running in ONE call.  Each problem goes through lbfgs_scalar's own arithmetic, so
+    its result is the one lbfgs_scalar -- and the device minimiser -- gives it alone.  Returns a list of
+    (x, f, g, iterations)."""
+    probs = [_lbfgs_scalar_problem(x0, lower, upper, iterations, g_tol, m, c1) for x0 in x0s]
+    out = [None] * len(probs)
+    pending = {i: next(prob) for i, prob in enumerate(probs)}
+    while pending:
+        idx = sorted(pending)
+        f, g = fg_multi(np.asarray(idx, dtype=np.intp), np.stack([pending[i] for i in idx]))
+        for k_, i in enumerate(idx):
+            try:
+                pending[i] = probs[i].send((f[k_], g[k_]))
+            except StopIteration as done:
+                out[i] = done.value
+                del pending[i]
+    return out
 
 
 def gp_optimize_multi(surs, theta0=None, lowerbounds=None, upperbounds=None, iterations=30, history=10,
