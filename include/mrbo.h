@@ -153,7 +153,8 @@ int mrbo_plan_destroy(mrbo_plan_t* plan);
  * lengthscale hypotheses on one data set, one after another).  The surrogates share d, N, kernel
  * and sigma_n2 -- a mismatch, S < 1 or an entry without X / L / c / y is MRBO_ERR_ARG, checked
  * before any HIP call -- and differ in X, L, c, y, lengthscale, period and fmini; the plan holds,
- * per surrogate, everything mrbo_plan_create derives from them.  p is shared: the box, rule, θ,
+ * per surrogate, everything mrbo_plan_create derives from them.  p is shared: the box (one box per
+ * surrogate: mrbo_plan_create_batch_boxes below), rule, θ,
  * solver options, cost model, and p->R = the restarts PER SURROGATE; so are the rnstream / nodes
  * and the xstarts of the calls.  Every workgroup of a launch serves one surrogate (grid
  * (⌈workgroups/S⌉, S), one set of per-XCD work queues per surrogate) and runs the code of a plain
@@ -177,10 +178,30 @@ int mrbo_plan_destroy(mrbo_plan_t* plan);
 int mrbo_plan_create_batch(const mrbo_surrogate_t* s, int32_t S, const mrbo_params_t* p, int32_t device,
                            mrbo_plan_t** out);
 
+/* Boxed plan: a surrogate batch whose surrogates each have their OWN box (the ARD trials of a BO
+ * loop, each on its whitened box).  lbs / ubs are HOST arrays d×S, the surrogate index slowest;
+ * p->lbs / p->ubs are ignored and may be NULL.  Every check of mrbo_plan_create_batch applies;
+ * further MRBO_ERR_ARG, before any HIP call: null lbs or ubs, a non-finite bound or lb > ub in
+ * any (dimension, surrogate) -- the message names the surrogate -- and a cost model on a box with
+ * ub <= lb in some dimension (the weights cost_w stay shared; u is normalised over the
+ * surrogate's own box).
+ *   On a boxed plan every call that takes xstarts reads S blocks, the surrogate index slowest:
+ *   mrbo_simulate_mc, mrbo_simulate_ghq, mrbo_simulate_control, mrbo_stochastic_solve and
+ *   mrbo_rollout_solve d×nstarts×S, mrbo_base_solve d×n×S (host-pointer staging follows).  There
+ *   is no flag: the plan decides, and a caller with equal starts replicates them.
+ *   mrbo_box_adam_step, the projection inside mrbo_rollout_solve and mrbo_pick_restart use the box
+ *   of the restart's surrogate (restart r of the R·S belongs to surrogate r / R).
+ * Block q of every output of every call is bit-identical to the same call on
+ * mrbo_plan_create(&s[q], p with box q) with starts q; S equal boxes and start blocks give the
+ * bits of mrbo_plan_create_batch; S = 1 is the plain plan on box 0 (xstarts then d×nstarts).
+ * Work orders stay MRBO_ERR_UNSUPPORTED at S > 1 (tests/test_gpu_batch_boxes.py).               */
+int mrbo_plan_create_batch_boxes(const mrbo_surrogate_t* s, int32_t S, const mrbo_params_t* p, const double* lbs,
+                                 const double* ubs, int32_t device, mrbo_plan_t** out);
+
 /* simulate_trajectory_mc for the R×M trajectories of the plan.
  *   x0s        d×R          start of each restart (tp.x0 / set_start!, rollout.jl:287)
  *   rnstream   M×(d+1)×(h+1) tp.rnstream_sequence (trajectory.jl:52-68), shared by restarts
- *   xstarts    d×nstarts    inner_solve_xstarts
+ *   xstarts    d×nstarts    inner_solve_xstarts (a boxed plan: d×nstarts×S, block q surrogate q's)
  *   dual_y_dx  d×h×M×R or NULL: δx of solve_dual_y call j (column j-1); NULL → counter RNG(seed)
  *   replay_x   d×h×M×R or NULL: inject policy points x_1..x_h instead of the inner solve
  *   values     M×R          resolutions
@@ -432,7 +453,8 @@ int mrbo_merge_moments(mrbo_plan_t* plan, int32_t nshards, const double* moments
 int mrbo_eval_base(mrbo_plan_t* plan, int32_t P, const double* xs, double* out, uint32_t flags, void* stream);
 
 /* base_solve(s::Surrogate; spatial_lbs, spatial_ubs, xstart, θfixed) rbf_optim.jl:35-66 for each
- * of n starts (columns of xstarts, d×n; any n ≥ 1) on the plan's BASE surrogate, with the plan's
+ * of n starts (columns of xstarts, d×n; any n ≥ 1; a boxed plan: d×n×S, block q the starts of
+ * surrogate q) on the plan's BASE surrogate, with the plan's
  * rule, θ, box and solver options (the build's projected Newton, DESIGN.md §3, as the rollout's
  * inner solve): xmin d×n = the minimizers, fmin n = the minima of −α, status n (MRBO_ST_* bits
  * except ALL_NAN), evals MRBO_NCOUNTERS×n or NULL.  One wavefront per start.  The caller takes

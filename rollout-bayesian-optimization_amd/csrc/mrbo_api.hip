@@ -55,6 +55,8 @@ struct mrbo_plan {
   int device = 0;
   int d = 0, N = 0, RPL = 1, NR = 64, Npad = 64;
   int S = 1;                // base surrogates (mrbo_plan_create_batch); the scalars below: surrogate 0
+  int boxed = 0;            // mrbo_plan_create_batch_boxes at S > 1: lbs, ubs, dlbs, dubs hold d×S, dcost S tables,
+                            // and every xstarts argument S blocks
   mrbo_params_t p{};
   std::vector<double> lbs, ubs, cost_w;
   int kernel = 0;
@@ -410,6 +412,11 @@ static void fill_common(const mrbo_plan_t* P, KParams& kp) {
   kp.cost_tab = P->dcost;
   kp.stab = P->dstab;
   kp.S = P->S;
+  if (P->boxed) {   // surrogate_select moves to the workgroup's own box, starts and cost table
+    kp.box_stride = P->d;
+    kp.xs_stride = (long long)P->d * P->p.nstarts;
+    kp.cost_stride = 3ll * P->d;
+  }
   kp.newton_fused = P->newton_fused;
 }
 
@@ -585,10 +592,28 @@ int mrbo_plan_create(const mrbo_surrogate_t* s, const mrbo_params_t* p, int32_t 
   return mrbo_plan_create_batch(s, 1, p, device, out);
 }
 
+// boxl / boxu null: the shared box p->lbs / p->ubs; else d×S host bounds, surrogate slowest
+static int plan_create_impl(const mrbo_surrogate_t* sv, int32_t S, const mrbo_params_t* p, const double* boxl,
+                            const double* boxu, int32_t device, mrbo_plan_t** out);
+
 int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_params_t* p, int32_t device,
                            mrbo_plan_t** out) {
+  return plan_create_impl(sv, S, p, nullptr, nullptr, device, out);
+}
+
+int mrbo_plan_create_batch_boxes(const mrbo_surrogate_t* sv, int32_t S, const mrbo_params_t* p, const double* lbs,
+                                 const double* ubs, int32_t device, mrbo_plan_t** out) {
+  if (!sv || !p || !out || !lbs || !ubs) return fail(MRBO_ERR_ARG, "null argument");
+  return plan_create_impl(sv, S, p, lbs, ubs, device, out);
+}
+
+}  // extern "C"
+
+static int plan_create_impl(const mrbo_surrogate_t* sv, int32_t S, const mrbo_params_t* p, const double* boxl,
+                            const double* boxu, int32_t device, mrbo_plan_t** out) {
   if (!sv || !p || !out) return fail(MRBO_ERR_ARG, "null argument");
   *out = nullptr;
+  const bool boxes = boxl != nullptr;
   if (S < 1) return fail(MRBO_ERR_ARG, "S=%d: at least one surrogate", (int)S);
   const mrbo_surrogate_t* s = sv;   // surrogate 0: the shape every entry shares
   const int d = s->d, N = s->N;
@@ -605,7 +630,14 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
   if (N > 512) return fail(MRBO_ERR_UNSUPPORTED, "N=%d > 512 not compiled", N);
   if (d > 8 && N > 128) return fail(MRBO_ERR_UNSUPPORTED, "d=%d > 8 with N=%d > 128 not compiled", d, N);
   if (p->h < 0 || p->h > FMAX - 1) return fail(MRBO_ERR_UNSUPPORTED, "h=%d outside [0,%d]", p->h, FMAX - 1);
-  if (p->M < 1 || p->R < 1 || p->nstarts < 1 || !p->lbs || !p->ubs) return fail(MRBO_ERR_ARG, "bad params");
+  if (p->M < 1 || p->R < 1 || p->nstarts < 1 || (!boxes && (!p->lbs || !p->ubs))) return fail(MRBO_ERR_ARG, "bad params");
+  if (boxes)
+    for (int q = 0; q < S; ++q)
+      for (int a = 0; a < d; ++a) {
+        const double lo = boxl[(size_t)q * d + a], hi = boxu[(size_t)q * d + a];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
+          return fail(MRBO_ERR_ARG, "surrogate %d: bounds [%g, %g] of dimension %d (finite, lb <= ub)", q, lo, hi, a);
+      }
   if (p->rule != MRBO_RULE_EI && p->rule != MRBO_RULE_POI && p->rule != MRBO_RULE_LCB)
     return fail(MRBO_ERR_ARG, "unknown decision rule %d", (int)p->rule);
   if (s->kernel < 0 || s->kernel > 4) return fail(MRBO_ERR_ARG, "kernel id %d", s->kernel);
@@ -620,7 +652,10 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
       if (!std::isfinite(p->cost_w[a])) return fail(MRBO_ERR_ARG, "cost weight %d is not finite", a);
       if (p->cost == MRBO_COST_QUADRATIC && p->cost_w[a] < 0.0)
         return fail(MRBO_ERR_ARG, "quadratic cost weight %d = %g < 0", a, p->cost_w[a]);
-      if (!(p->ubs[a] > p->lbs[a])) return fail(MRBO_ERR_ARG, "cost model needs ub > lb (dimension %d)", a);
+      if (!boxes && !(p->ubs[a] > p->lbs[a])) return fail(MRBO_ERR_ARG, "cost model needs ub > lb (dimension %d)", a);
+      for (int q = 0; boxes && q < S; ++q)   // the same rule on every surrogate's own box
+        if (!(boxu[(size_t)q * d + a] > boxl[(size_t)q * d + a]))
+          return fail(MRBO_ERR_ARG, "cost model needs ub > lb (dimension %d, surrogate %d)", a, q);
     }
   }
   for (int q = 0; q < S; ++q)
@@ -636,8 +671,11 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
   P->NR = 64 * P->RPL;
   P->Npad = P->NR;
   P->p = *p;
-  P->lbs.assign(p->lbs, p->lbs + d);
-  P->ubs.assign(p->ubs, p->ubs + d);
+  // per-surrogate boxes at S = 1 are the plain plan on box 0
+  P->boxed = (boxes && S > 1) ? 1 : 0;
+  const size_t nbox = P->boxed ? (size_t)S : 1;
+  P->lbs.assign(boxes ? boxl : p->lbs, (boxes ? boxl : p->lbs) + nbox * d);
+  P->ubs.assign(boxes ? boxu : p->ubs, (boxes ? boxu : p->ubs) + nbox * d);
   P->p.lbs = nullptr;
   P->p.ubs = nullptr;
   if (p->cost != MRBO_COST_NONE) P->cost_w.assign(p->cost_w, p->cost_w + d);
@@ -827,8 +865,8 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
   bool ok = hipMalloc(&P->dX0, sizeof(double) * X0.size()) == hipSuccess &&
             hipMalloc(&P->dc0, sizeof(double) * c0.size()) == hipSuccess &&
             hipMalloc(&P->dLinv, sizeof(double) * packed_all.size()) == hipSuccess &&
-            hipMalloc(&P->dlbs, sizeof(double) * d) == hipSuccess &&
-            hipMalloc(&P->dubs, sizeof(double) * d) == hipSuccess &&
+            hipMalloc(&P->dlbs, sizeof(double) * d * nbox) == hipSuccess &&
+            hipMalloc(&P->dubs, sizeof(double) * d * nbox) == hipSuccess &&
             hipMalloc(&P->dwork, sizeof(double) * (size_t)slots * P->work_stride) == hipSuccess &&
             (!P->batch || !ks.square ||
              hipMalloc(&P->dytab, sizeof(double) * (size_t)ns * P->NR * S) == hipSuccess) &&
@@ -839,21 +877,22 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
              hipMalloc(&P->drtab, sizeof(double) * (size_t)rtab_stride(d, P->NR) * p->R * S) == hipSuccess) &&
             hipMalloc(&P->dqueue, sizeof(int) * MRBO_QUEUE_INTS * S) == hipSuccess &&
             (S == 1 || hipMalloc(&P->dstab, sizeof(SurTab) * S) == hipSuccess) &&
-            (P->p.cost == MRBO_COST_NONE || hipMalloc(&P->dcost, sizeof(double) * 3 * d) == hipSuccess);
+            (P->p.cost == MRBO_COST_NONE || hipMalloc(&P->dcost, sizeof(double) * 3 * d * nbox) == hipSuccess);
   if (ok && P->p.cost != MRBO_COST_NONE) {
-    std::vector<double> tab(3 * (size_t)d);
-    for (int a = 0; a < d; ++a) {
-      tab[a] = P->lbs[a];
-      tab[d + a] = P->ubs[a] - P->lbs[a];
-      tab[2 * d + a] = P->cost_w[a];
-    }
-    ok = hipMemcpy(P->dcost, tab.data(), sizeof(double) * 3 * d, hipMemcpyHostToDevice) == hipSuccess;
+    std::vector<double> tab(3 * (size_t)d * nbox);   // one [lb, del, w] per box, the weights shared
+    for (size_t q = 0; q < nbox; ++q)
+      for (int a = 0; a < d; ++a) {
+        tab[3 * d * q + a] = P->lbs[q * d + a];
+        tab[3 * d * q + d + a] = P->ubs[q * d + a] - P->lbs[q * d + a];
+        tab[3 * d * q + 2 * d + a] = P->cost_w[a];
+      }
+    ok = hipMemcpy(P->dcost, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) == hipSuccess;
   }
   ok = ok && hipMemcpy(P->dX0, X0.data(), sizeof(double) * X0.size(), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(P->dc0, c0.data(), sizeof(double) * c0.size(), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(P->dLinv, packed_all.data(), sizeof(double) * packed_all.size(), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(P->dlbs, P->lbs.data(), sizeof(double) * d, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(P->dubs, P->ubs.data(), sizeof(double) * d, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(P->dlbs, P->lbs.data(), sizeof(double) * d * nbox, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(P->dubs, P->ubs.data(), sizeof(double) * d * nbox, hipMemcpyHostToDevice) == hipSuccess &&
        hipMemset(P->dwork, 0, sizeof(double) * (size_t)slots * P->work_stride) == hipSuccess;
   if (ok && S > 1) {   // the per-surrogate table: block q of every image and start table
     for (int q = 0; q < S; ++q) {
@@ -876,6 +915,8 @@ int mrbo_plan_create_batch(const mrbo_surrogate_t* sv, int32_t S, const mrbo_par
   *out = P;
   return MRBO_OK;
 }
+
+extern "C" {
 
 int mrbo_plan_destroy(mrbo_plan_t* P) {
   if (!P) return MRBO_OK;
@@ -926,7 +967,7 @@ static int simulate_common(mrbo_plan_t* P, const double* x0s, const double* rnst
   if (host) {
     if (sg.in(x0s, (size_t)d * R, &kp.x0s) || sg.in(rnstream, (size_t)M * (d + 1) * (h + 1), &kp.rn) ||
         sg.in(ghq_nodes, (size_t)M * (h + 1), &kp.ghq_nodes) || sg.in(ghq_w, (size_t)M * (h + 1), &kp.ghq_w) ||
-        sg.in(xstarts, (size_t)d * P->p.nstarts, &kp.xstarts) ||
+        sg.in(xstarts, (size_t)d * P->p.nstarts * (P->boxed ? S : 1), &kp.xstarts) ||
         sg.in(dual_y_dx, (size_t)d * std::max(h, 1) * T, &kp.dual_y) ||
         sg.in(replay_x, (size_t)d * std::max(h, 1) * T, &kp.replay) || sg.out(T, values, &dvalues) ||
         sg.out((size_t)d * T, with_grad ? grad_x : nullptr, &dgx) || sg.out(T, with_grad ? grad_theta : nullptr, &dgt) ||
@@ -1240,7 +1281,7 @@ int Ascent::run(double* x0s, const double* rnstream, const double* xstarts, cons
   // with the control variate every rollout launch is followed by its horizon-0 control launch: its
   // status words stand behind the rollout's, so that one check reads both
   nst = cv ? 2 * T : T;
-  const size_t nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts;
+  const size_t nrn = (size_t)M * (d + 1) * (h + 1), nxs = (size_t)d * P->p.nstarts * (P->boxed ? P->S : 1);
   const size_t ndual = (size_t)d * std::max(h, 1) * T;
   const double sample_size = o->sample_size > 0 ? o->sample_size : (double)M;
   x0 = host ? (double*)solve_slot(P, SLOT_X0, sizeof(double) * nx) : x0s;
@@ -1390,7 +1431,7 @@ int mrbo_box_adam_step(mrbo_plan_t* P, const double* eto, double* x0s, int32_t* 
   if (hipSetDevice(P->device) != hipSuccess) return fail(MRBO_ERR_HIP, "hipSetDevice");
   const double c1 = 1.0 - std::pow(beta1, (double)t), c2 = 1.0 - std::pow(beta2, (double)t);
   launch_box_adam_step((hipStream_t)stream, eto, x0s, (int*)active, m, v, P->p.R * P->S, P->d, P->dlbs, P->dubs,
-                       sample_size, eta, beta1, beta2, eps, c1, c2);
+                       P->p.R, P->boxed ? P->d : 0, sample_size, eta, beta1, beta2, eps, c1, c2);
   HIP_TRY(hipGetLastError());
   return MRBO_OK;
 }
@@ -1400,7 +1441,7 @@ static int pick_common(mrbo_plan_t* P, const double* x, const double* eto, int i
                        int32_t* pick, double* means, int* novel, hipStream_t st) {
   PickParams q{};
   q.d = P->d; q.N = P->N; q.R = P->p.R; q.S = P->S; q.ldX = P->NR; q.incumbent = incumbent != 0;
-  q.X0 = P->dX0; q.lbs = P->dlbs; q.ubs = P->dubs;
+  q.X0 = P->dX0; q.lbs = P->dlbs; q.ubs = P->dubs; q.box_stride = P->boxed ? P->d : 0;
   q.x = x; q.eto = eto; q.means = means; q.novel = novel; q.xnext = xnext; q.mean = mean; q.pick = (int*)pick;
   launch_pick_restart(st, q);
   HIP_TRY(hipGetLastError());
@@ -1451,7 +1492,7 @@ int mrbo_rollout_solve(mrbo_plan_t* P, double* x0s, const double* rnstream, cons
   // rollout_solve's tail: the end points projected onto the box, one launch without gradients at
   // them with nothing skipped, the ETO means, the pick.  Its check goes to the ring slot after the
   // last iteration's: read long ago, and not one of the (at most LAG) checks still in flight.
-  launch_box_project(st, a.x0, (long long)a.nx, d, P->dlbs, P->dubs);
+  launch_box_project(st, a.x0, (long long)a.nx, d, P->dlbs, P->dubs, P->p.R, P->boxed ? d : 0);
   HIP_TRY(hipGetLastError());
   rc = mrbo_simulate_mc(P, a.x0, a.rn, a.xs, nullptr, nullptr, a.vals, nullptr, nullptr, a.status, nullptr, nullptr,
                         nullptr, MRBO_FLAG_NO_GRADIENT, st);
@@ -1575,6 +1616,7 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   kp.with_gradient = 0;
   kp.xs_lds = 0;
   kp.batch = 0;
+  kp.xs_stride = 0;   // a boxed plan: d×n×S starts, addressed by the global item index
   Stage sg(P);
   const double* dxs = xstarts;
   double *dx = xmin, *df = fmin;
@@ -1583,7 +1625,7 @@ int mrbo_base_solve(mrbo_plan_t* P, int32_t n, const double* xstarts, double* xm
   const bool host = flags & MRBO_FLAG_HOST_POINTERS;
   const size_t S = (size_t)P->S;   // the n starts on each surrogate: every output holds S blocks
   if (host) {
-    if (sg.in(xstarts, (size_t)d * n, &dxs) || sg.out((size_t)d * n * S, xmin, &dx) ||
+    if (sg.in(xstarts, (size_t)d * n * (P->boxed ? S : 1), &dxs) || sg.out((size_t)d * n * S, xmin, &dx) ||
         sg.out((size_t)n * S, fmin, &df) || sg.out((size_t)n * S, status, &dst) ||
         sg.out((size_t)NCOUNT * n * S, evals, &dev))
       return fail(MRBO_ERR_NOMEM, "staging allocation failed");

@@ -136,6 +136,12 @@ struct KParams {
   // (a pointer to a table, not array members: see cost_tab)
   const SurTab* stab;
   int S;
+  // Boxed plan (mrbo_plan_create_batch_boxes): every surrogate has its own box, inner starts and
+  // cost table.  lbs / ubs hold d×S doubles, xstarts d×nstarts×S, cost_tab S blocks of 3d; the
+  // strides, in doubles, take surrogate_select to block blockIdx.y.  All zero on every other plan
+  // (box_stride != 0 marks the boxed plan; xs_stride is zero in its base-solve launches, whose
+  // global item index addresses the d×n×S starts already)
+  long long box_stride, xs_stride, cost_stride;
   // Restart table (square full-wave layout; null: every trajectory evaluates step 0 itself): row
   // r + blockIdx.y·R holds what step 0 of restart r leaves behind -- the EV_DRAW evaluation of the
   // base surrogate at x0_r and the factor of its draw, the same for all M samples.  Written by

@@ -3095,8 +3095,13 @@ __device__ __forceinline__ void surrogate_select(KParams& kp) {
   kp.fmin_base = e.fmin_base; kp.fmini = e.fmini;
   kp.gcert_mu = e.gcert_mu; kp.gcert_d2 = e.gcert_d2;
   kp.work += s * gridDim.x * (blockDim.x / WAVE) * kp.work_stride;
-  // mrbo_base_solve: item tr + s·n of surrogate s starts from column tr of the shared starts
-  if (kp.base_solve) kp.xstarts -= s * kp.T * kp.d;
+  // boxed plan: this surrogate's box, inner starts and cost table (the strides are zero elsewhere)
+  kp.lbs += s * kp.box_stride; kp.ubs += s * kp.box_stride;
+  kp.xstarts += s * kp.xs_stride;
+  kp.cost_tab += s * kp.cost_stride;
+  // mrbo_base_solve: item tr + s·n of surrogate s starts from column tr of the shared starts (a
+  // boxed plan holds d×n×S starts, which the global item index addresses as it is)
+  if (kp.base_solve && !kp.box_stride) kp.xstarts -= s * kp.T * kp.d;
 }
 // the first queue head of this workgroup's surrogate, in ints from kp.queue
 __device__ __forceinline__ int surrogate_queue() { return (int)blockIdx.y * MRBO_QUEUE_INTS; }

@@ -20,21 +20,24 @@ __device__ __forceinline__ bool eswavs_stops(const double* e, int d, double samp
 }
 
 // eswavs + BoxAdam.update for every active restart (R: all restarts of the plan, R·S on a
-// surrogate batch); c1 = 1 − β1^t, c2 = 1 − β2^t formed on the host
+// surrogate batch); c1 = 1 − β1^t, c2 = 1 − β2^t formed on the host.  Restart r uses the box of
+// surrogate r / Rs, box_stride doubles per surrogate into lbs / ubs (0: one box shared by all)
 void launch_box_adam_step(hipStream_t st, const double* eto, double* x0s, int* active, double* m, double* v, int R,
-                          int d, const double* lbs, const double* ubs, double sample_size, double eta, double b1,
-                          double b2, double eps, double c1, double c2);
+                          int d, const double* lbs, const double* ubs, int Rs, long long box_stride,
+                          double sample_size, double eta, double b1, double b2, double eps, double c1, double c2);
 
-// x ← clip(x, lb, ub) for the n = d·R coordinates of x, a NaN kept
-void launch_box_project(hipStream_t st, double* x, long long n, int d, const double* lbs, const double* ubs);
+// x ← clip(x, lb, ub) for the n = d·Rs·S coordinates of x, a NaN kept; boxes as in the step
+void launch_box_project(hipStream_t st, double* x, long long n, int d, const double* lbs, const double* ubs, int Rs,
+                        long long box_stride);
 
 struct PickParams {
   int d, N, R, S;
   int ldX;                 // X0 is [S][d][ldX], the first N entries of a row observed
   int incumbent;
   const double* X0;        // the plan's device copy of the observed points
-  const double* lbs;
+  const double* lbs;       // surrogate q's box at lbs + q·box_stride (0: one box shared by all)
   const double* ubs;
+  long long box_stride;
   const double* x;         // d×R×S
   const double* eto;       // R·S rows of W = 2 + 2d + 2, the mean first
   double* means;           // R×S: the means, −∞ where not finite (never null here)

@@ -25,12 +25,16 @@ __device__ __forceinline__ double clip(double v, double lo, double hi) {
 }
 
 // One thread per restart, as mrbo_adam_step: Adam's update on u = (x − lb)/w with the gradient g·w.
+// Restart r of the R = Rs·S restarts belongs to surrogate r / Rs, whose box starts box_stride doubles
+// after its predecessor's (a boxed plan: d; a shared box: 0).
 __global__ void __launch_bounds__(64) box_adam_kernel(const double* eto, double* x0s, int* active, double* m, double* v,
-                                                      int R, int d, const double* lbs, const double* ubs,
-                                                      double sample_size, double eta, double b1, double b2,
-                                                      double eps, double c1, double c2) {
+                                                      int R, int d, const double* lbs, const double* ubs, int Rs,
+                                                      long long box_stride, double sample_size, double eta, double b1,
+                                                      double b2, double eps, double c1, double c2) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R || !active[r]) return;
+  lbs += (r / Rs) * box_stride;
+  ubs += (r / Rs) * box_stride;
   const double* e = eto + (size_t)(2 + 2 * d + 2) * r;
   if (eswavs_stops(e, d, sample_size)) {
     active[r] = 0;
@@ -51,11 +55,12 @@ __global__ void __launch_bounds__(64) box_adam_kernel(const double* eto, double*
   }
 }
 
+// coordinate k of the d·Rs·S: dimension k % d of restart k / d, surrogate k / (d·Rs)
 __global__ void __launch_bounds__(64) box_project_kernel(double* x, long long n, int d, const double* lbs,
-                                                         const double* ubs) {
+                                                         const double* ubs, int Rs, long long box_stride) {
   const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const int a = (int)(k % d);
+  const long long a = k % d + (k / d / Rs) * box_stride;
   x[k] = clip(x[k], lbs[a], ubs[a]);
 }
 
@@ -73,6 +78,8 @@ __global__ void __launch_bounds__(PICK_THREADS) pick_kernel(PickParams p) {
   const int d = p.d, R = p.R, W = 2 + 2 * d + 2;
   const double ninf = -__builtin_inf();
   const double* X = p.X0 + (size_t)q * d * p.ldX;
+  const double* lbs = p.lbs + q * p.box_stride;   // workgroup q uses box q (a shared box: stride 0)
+  const double* ubs = p.ubs + q * p.box_stride;
   if (tid == 0) any_novel = 0;
   __syncthreads();
   for (int r = tid; r < R; r += PICK_THREADS) {
@@ -89,7 +96,7 @@ __global__ void __launch_bounds__(PICK_THREADS) pick_kernel(PickParams p) {
       for (int j = 0; j < p.N; ++j) {
         double mx = 0.0;
         for (int a = 0; a < d; ++a) {
-          const double t = fabs((xr[a] - X[(size_t)a * p.ldX + j]) / (p.ubs[a] - p.lbs[a]));
+          const double t = fabs((xr[a] - X[(size_t)a * p.ldX + j]) / (ubs[a] - lbs[a]));
           if (t != t) nan = true;
           else if (t > mx) mx = t;
         }
@@ -132,14 +139,16 @@ __global__ void __launch_bounds__(PICK_THREADS) pick_kernel(PickParams p) {
 }  // namespace
 
 void launch_box_adam_step(hipStream_t st, const double* eto, double* x0s, int* active, double* m, double* v, int R,
-                          int d, const double* lbs, const double* ubs, double sample_size, double eta, double b1,
-                          double b2, double eps, double c1, double c2) {
+                          int d, const double* lbs, const double* ubs, int Rs, long long box_stride,
+                          double sample_size, double eta, double b1, double b2, double eps, double c1, double c2) {
   hipLaunchKernelGGL(box_adam_kernel, dim3((R + 63) / 64), dim3(64), 0, st, eto, x0s, active, m, v, R, d, lbs, ubs,
-                     sample_size, eta, b1, b2, eps, c1, c2);
+                     Rs, box_stride, sample_size, eta, b1, b2, eps, c1, c2);
 }
 
-void launch_box_project(hipStream_t st, double* x, long long n, int d, const double* lbs, const double* ubs) {
-  hipLaunchKernelGGL(box_project_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, x, n, d, lbs, ubs);
+void launch_box_project(hipStream_t st, double* x, long long n, int d, const double* lbs, const double* ubs, int Rs,
+                        long long box_stride) {
+  hipLaunchKernelGGL(box_project_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, x, n, d, lbs, ubs, Rs,
+                     box_stride);
 }
 
 void launch_pick_restart(hipStream_t st, const PickParams& p) {

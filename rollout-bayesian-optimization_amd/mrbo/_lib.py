@@ -41,6 +41,7 @@ EXPORTS = [
     "mrbo_simulate_control", "mrbo_eto_reduce_cv", "mrbo_plan_set_control_variate",
     "mrbo_gp_fit_profile_multi", "mrbo_gp_optimize_profile_multi",
     "mrbo_gp_fit_ard_multi", "mrbo_gp_optimize_ard_multi",
+    "mrbo_plan_create_batch_boxes",
 ]
 
 MRBO_OPT_SGA, MRBO_OPT_ADAM, MRBO_OPT_BOX_ADAM = 0, 1, 2
@@ -111,6 +112,9 @@ def load():
                                    ctypes.POINTER(_vp)]
     L.mrbo_plan_create_batch.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32, ctypes.POINTER(ParamsDesc),
                                          ctypes.c_int32, ctypes.POINTER(_vp)]
+    L.mrbo_plan_create_batch_boxes.argtypes = [ctypes.POINTER(SurrogateDesc), ctypes.c_int32,
+                                               ctypes.POINTER(ParamsDesc), ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.POINTER(_vp)]
     L.mrbo_plan_destroy.argtypes = [_vp]
     L.mrbo_simulate_mc.argtypes = [_vp] + [_vp] * 12 + [ctypes.c_uint32, _vp]
     L.mrbo_simulate_ghq.argtypes = [_vp] + [_vp] * 13 + [ctypes.c_uint32, _vp]

@@ -125,7 +125,10 @@ def _device_solve(plan, x0, tp, es, sgd_iterations, eta, solver, incumbent, vari
     if variance_reduction:
         plan.set_control_variate(True)
     try:
-        return plan.rollout_solve_host(x0, tp.rnstream_sequence, es.get_starts(),
+        # per-surrogate boxes: tp, es lists of S (equal MC streams), the starts d×nstarts×S
+        xstarts = np.stack([e.get_starts() for e in es], axis=2) if isinstance(es, (list, tuple)) else es.get_starts()
+        tp = tp[0] if isinstance(tp, (list, tuple)) else tp
+        return plan.rollout_solve_host(x0, tp.rnstream_sequence, xstarts,
                                        optimizer="sga" if solver == "sga" else "box_adam", iterations=sgd_iterations,
                                        eta=eta, sample_size=tp.mc_iters, incumbent=incumbent)
     finally:
@@ -191,8 +194,16 @@ def rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts,
     that surrogate alone.  `trace`, a list, receives one dict per call (x0 d×R×S, the final points,
     the final ETO means R×S, the picks; the host loop adds its `history`).  device_solve=True: one
     mrbo_rollout_solve call on the surrogate batch instead of the host-driven loop, same results.
-    variance_reduction=True: the control-variate ETO rows, as rollout_solve."""
+    variance_reduction=True: the control-variate ETO rows, as rollout_solve.
+
+    lbs, ubs of shape (d, S): surrogate q solves over its own box [lbs[:, q], ubs[:, q]] -- its own
+    Sobol batch, incumbent start, inner starts, BoxAdam box, projection and pick -- on ONE boxed plan
+    (RolloutPlan.from_surrogates), one launch per iteration or one mrbo_rollout_solve call; result q is
+    rollout_solve(surs[q], lbs[:, q], ubs[:, q], ...)."""
     lbs, ubs = np.asarray(lbs, float), np.asarray(ubs, float)
+    if lbs.ndim == 2 or ubs.ndim == 2:
+        return _rollout_solve_boxes(list(surs), lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
+                                    theta, eta, device, solver, incumbent, trace, device_solve, variance_reduction)
     batch = generate_batch(batch_size, lbs, ubs)
     batches = [np.hstack([batch, incumbent_start(s, lbs, ubs)[:, None]]) if incumbent else batch for s in surs]
     x0 = np.stack(batches, axis=2)                                     # d×R×S
@@ -220,6 +231,55 @@ def rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts,
     for q, s in enumerate(surs):
         xq = x[:, :, q]
         k, means = pick_restart(s, xq, brs[q].etos(with_gradient=False), lbs, ubs, incumbent)
+        out.append((xq[:, k].copy(), float(means[k])))
+        picks.append(k)
+        all_means.append(means)
+    if trace is not None:
+        trace.append(dict(batch=x0, x=x.copy(), means=np.stack(all_means, axis=1), pick=picks, history=history))
+    return out
+
+
+def _rollout_solve_boxes(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations, theta, eta, device,
+                         solver, incumbent, trace, device_solve, variance_reduction):
+    """rollout_solve_multi with per-surrogate boxes lbs, ubs (d×S): everything rollout_solve derives
+    from the box once per surrogate, the launches on one boxed plan."""
+    from .engine import check_bounds
+    S = len(surs)
+    check_bounds(lbs, ubs, surs[0].X.shape[0], S)
+    batches, tps, ess = [], [], []
+    for q, s in enumerate(surs):
+        lq, uq = np.ascontiguousarray(lbs[:, q]), np.ascontiguousarray(ubs[:, q])
+        batch = generate_batch(batch_size, lq, uq)
+        batches.append(np.hstack([batch, incumbent_start(s, lq, uq)[:, None]]) if incumbent else batch)
+        tps.append(TrajectoryParameters(start=batch[:, 0], hypers=[theta], horizon=horizon, mc_iterations=mc_samples,
+                                        use_low_discrepancy_sequence=True, spatial_lowerbounds=lq,
+                                        spatial_upperbounds=uq))
+        ess.append(ExperimentSetup(tps[q], number_of_starts=starts))
+    x0 = np.stack(batches, axis=2)                                     # d×R×S
+    trajs = [Trajectory(s, FantasySurrogate(s, horizon), start=batches[q][:, 0], hypers=[theta], horizon=horizon)
+             for q, s in enumerate(surs)]
+    if device_solve:
+        from .rollout import per_surrogate_parameters
+        per_surrogate_parameters(tps, S)   # the launch has one MC stream
+        plan = _plan_for_multi(surs, horizon, tps[0].rnstream_sequence.shape[0], x0.shape[1],
+                               ess[0].get_starts().shape[1], lbs, ubs, trajs[0].θ[0], device, {})
+        r = _device_solve(plan, x0, tps, ess, sgd_iterations, eta, solver, incumbent, variance_reduction)
+        if trace is not None:
+            trace.append(dict(batch=x0, x=r["x"], means=r["means"], pick=[int(k) for k in r["pick"]],
+                              result=r["result"]))
+        return [(r["xnext"][:, q].copy(), float(r["mean"][q])) for q in range(S)]
+    opts = [[StandardSGA(η=eta) if solver == "sga" else BoxAdam(lbs[:, q], ubs[:, q], η=eta)
+             for _ in range(x0.shape[1])] for q in range(S)]
+    x, history = stochastic_solve_multi(opts, surs, tps, ess, x0, Ts=trajs, iterations=sgd_iterations, device=device,
+                                        variance_reduction=variance_reduction)
+    x = np.clip(x, lbs[:, None, :], ubs[:, None, :])
+    xstarts = np.stack([e.get_starts() for e in ess], axis=2)
+    brs = simulate_trajectory_mc_multi(trajs, tps, x, xstarts, with_gradient=False, device=device,
+                                       variance_reduction=variance_reduction)
+    out, picks, all_means = [], [], []
+    for q, s in enumerate(surs):
+        xq = x[:, :, q]
+        k, means = pick_restart(s, xq, brs[q].etos(with_gradient=False), lbs[:, q], ubs[:, q], incumbent)
         out.append((xq[:, k].copy(), float(means[k])))
         picks.append(k)
         all_means.append(means)
@@ -268,6 +328,27 @@ def _ard_myopic_pick(s, lbs, ubs, guesses, theta, device):
     return np.clip(s.unwhiten(zs[:, findmin_candidates(zs, fs)]), lbs, ubs)
 
 
+def _ard_rollout_picks(surs, lbs, ubs, *args, **kw):
+    """_ard_rollout_pick for the lockstep trials `surs` as ONE rollout_solve_multi on their `inner`
+    surrogates over their whitened boxes (a boxed plan); each xnext mapped back and clipped per trial."""
+    boxes = [s.whitened_box(lbs, ubs) for s in surs]
+    zl, zu = np.stack([b[0] for b in boxes], axis=1), np.stack([b[1] for b in boxes], axis=1)
+    picks = rollout_solve_multi([s.inner for s in surs], zl, zu, *args, **kw)
+    return [(np.clip(s.unwhiten(znext), lbs, ubs), mean) for s, (znext, mean) in zip(surs, picks)]
+
+
+def _ard_myopic_picks(surs, lbs, ubs, guesses, theta, device):
+    """_ard_myopic_pick for the lockstep trials `surs` as ONE base_solve_multi on their `inner`
+    surrogates: boxes and guesses whitened per trial, minimisers mapped back and clipped per trial."""
+    from .rbf_optim import base_solve_multi, findmin_candidates
+    boxes = [s.whitened_box(lbs, ubs) for s in surs]
+    zl, zu = np.stack([b[0] for b in boxes], axis=1), np.stack([b[1] for b in boxes], axis=1)
+    zg = np.stack([s.whiten(guesses) for s in surs], axis=2)
+    zs, fs, _ = base_solve_multi([s.inner for s in surs], zl, zu, zg, [theta], device=device)
+    return [np.clip(s.unwhiten(zs[:, findmin_candidates(zs[:, :, q], fs[:, q]), q]), lbs, ubs)
+            for q, s in enumerate(surs)]
+
+
 def _check_ard(ard, optimize):
     if ard and not optimize:
         raise ValueError("ard=True needs optimize=True: the ARD lengthscales are what the refit fits "
@@ -312,8 +393,9 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
     device_mle as one device call; with parallel_trials > 1 one batched refit per chunk), runs the
     acquisition solve on the surrogate's `inner` over the whitened box z = x/ells, maps xnext back and clips
     it to the raw box.  The inner solve's x_tol and the outer ascent's `eta` therefore act in whitened
-    coordinates, i.e. in units of the fitted lengthscales.  Lockstep trials solve one trial at a time
-    (their whitened boxes differ).  Every result carries `ells`, the trial's final lengthscales."""
+    coordinates, i.e. in units of the fitted lengthscales.  Lockstep trials solve together: their whitened
+    boxes differ, so the chunk's solve runs on a boxed plan (per-surrogate boxes, rollout_solve_multi with
+    (d, S) bounds).  Every result carries `ells`, the trial's final lengthscales."""
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     _check_ard(ard, optimize)
     testfn = TESTFNS[function_name]()
@@ -353,11 +435,10 @@ def run(function_name, output_dir, budget=15, trials=60, starts=16, horizon=0, m
             mle_times = np.zeros(budget)   # wall time of the chunk's batched refit per budget step
             for b in range(budget):
                 t0 = time.perf_counter()
-                if ard:   # the trials' whitened boxes differ: one solve per trial
-                    picks = [_ard_rollout_pick(s, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
+                if ard:   # the trials' whitened boxes differ: one solve on a boxed plan
+                    picks = _ard_rollout_picks(surs, lbs, ubs, horizon, mc_samples, batch_size, starts, sgd_iterations,
                                                theta, eta=eta, device=device, solver=solver, incumbent=incumbent,
                                                device_solve=device_solve, variance_reduction=variance_reduction)
-                             for s in surs]
                 else:
                     picks = rollout_solve_multi(surs, lbs, ubs, horizon, mc_samples, batch_size, starts,
                                                 sgd_iterations, theta, eta=eta, device=device, solver=solver,
@@ -468,7 +549,8 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
     ard=True (needs optimize=True, else ValueError; not with the no_repeat diagnostic): ARDSurrogates as in
     run -- the ells refit in [0.1, 5]^d after every observation, the multistart solve on `inner` with the
     guesses and the box whitened (its x_tol in whitened coordinates, units of the fitted lengthscales),
-    the minimiser mapped back and clipped to the raw box; lockstep trials solve one trial at a time."""
+    the minimiser mapped back and clipped to the raw box; lockstep trials solve in one launch on a boxed
+    plan (base_solve_multi with (d, S) bounds and whitened guesses d×n×S)."""
     from .rbf_optim import base_solve_batch, base_solve_multi, findmin_candidates, multistart_base_solve
     parallel_trials = _check_parallel_trials(parallel_trials, reuse_surrogate)
     _check_ard(ard, optimize)
@@ -514,8 +596,8 @@ def run_myopic(function_name, output_dir, budget=100, trials=60, starts=64, seed
             for b in range(budget):
                 t0 = time.perf_counter()
                 w = (ubs - lbs) * solve_margin
-                if ard:   # the trials' whitened boxes differ: one solve per trial
-                    ard_next = [_ard_myopic_pick(s, lbs + w, ubs - w, guesses, theta, device) for s in surs]
+                if ard:   # the trials' whitened boxes differ: one solve on a boxed plan
+                    ard_next = _ard_myopic_picks(surs, lbs + w, ubs - w, guesses, theta, device)
                 else:
                     xs_, fs_, _ = base_solve_multi(surs, lbs + w, ubs - w, guesses, [theta], device=device)
                 dt = time.perf_counter() - t0

@@ -36,6 +36,19 @@ def from_device(t, shape):
     return t.detach().cpu().numpy().reshape(shape, order="F")
 
 
+def check_bounds(lbs, ubs, d, S):
+    """The bounds of a plan for S surrogates of dimension d: both (d,) -- one shared box, returns
+    False -- or both (d, S) -- per-surrogate boxes, returns True.  Anything else, a mix of the two
+    included, is a ValueError."""
+    sl, su = np.shape(lbs), np.shape(ubs)
+    if sl == (d,) and su == (d,):
+        return False
+    if sl == (d, S) and su == (d, S):
+        return True
+    raise ValueError(f"bounds must both be (d,) = {(d,)} (a shared box) or both (d, S) = {(d, S)} (one box per "
+                     f"surrogate); got lbs {sl}, ubs {su}")
+
+
 SURROGATE_KEYS = ("X", "L", "c", "y", "kernel", "lengthscale", "fmini")   # + sigma_n2, period (optional)
 
 
@@ -54,7 +67,13 @@ class RolloutPlan:
         and optionally sigma_n2 (default 1e-6) and period (default 1).  They share d, N, kernel and
         sigma_n2; R is the number of restarts PER surrogate, and everything else is shared.  Inputs
         and outputs carry the surrogate index slowest (x0s d×R×S, values M×R×S, ...); block q of every
-        output is bit-identical to a plain plan on surrogate q."""
+        output is bit-identical to a plain plan on surrogate q.
+
+        lbs, ubs of shape (d,): one box shared by all.  Shape (d, S): a boxed plan
+        (mrbo_plan_create_batch_boxes), surrogate q on its own box [lbs[:, q], ubs[:, q]]; every
+        xstarts argument of its calls is then d×nstarts×S (base solves: d×n×S), block q the inner
+        starts of surrogate q, and block q of every output is bit-identical to a plain plan on
+        surrogate q over box q with starts q."""
         surrogates = list(surrogates)
         if not surrogates:
             raise ValueError("from_surrogates needs at least one surrogate")
@@ -84,9 +103,15 @@ class RolloutPlan:
                                         float(s.get("period", 1.0)))
         self._X, self._L, self._c, self._y = self._keep[0]
         self.d, self.N = self._X.shape
+        per_surrogate = check_bounds(lbs, ubs, self.d, self.S)
         pd = self._params(h, M, R, nstarts, lbs, ubs, theta, device, opts)
         h_ = ctypes.c_void_p()
-        _lib.check(self.lib.mrbo_plan_create_batch(sds, self.S, ctypes.byref(pd), int(device), ctypes.byref(h_)))
+        if per_surrogate:
+            _lib.check(self.lib.mrbo_plan_create_batch_boxes(sds, self.S, ctypes.byref(pd), self._lbs.ctypes.data_as(dp),
+                                                             self._ubs.ctypes.data_as(dp), int(device),
+                                                             ctypes.byref(h_)))
+        else:
+            _lib.check(self.lib.mrbo_plan_create_batch(sds, self.S, ctypes.byref(pd), int(device), ctypes.byref(h_)))
         self.handle = h_
 
     def _params(self, h, M, R, nstarts, lbs, ubs, theta, device, opts):
@@ -95,7 +120,10 @@ class RolloutPlan:
         o.update(opts)
         self.opts = o
         self.h, self.M, self.R, self.nstarts = int(h), int(M), int(R), int(nstarts)
-        self._lbs, self._ubs = _f64(lbs).ravel(), _f64(ubs).ravel()
+        # flat column-major: d on a shared box, d×S (surrogate slowest) with per-surrogate boxes
+        self._lbs, self._ubs = _f64(lbs).ravel(order="F"), _f64(ubs).ravel(order="F")
+        # a boxed plan: S > 1 surrogates on their own boxes (one surrogate on "its own" box is the plain plan)
+        self.boxed = np.ndim(lbs) == 2 and self.S > 1
         self.theta = float(theta)
         self.device = device
         dp = ctypes.POINTER(ctypes.c_double)
@@ -110,6 +138,27 @@ class RolloutPlan:
                              int(o["seed"]), int(o.get("sample_offset", 0)), int(o.get("samples_total", 0)),
                              ck, float(o["cost_c0"]), self._cost_w.ctypes.data_as(dp) if ck else None)
         return pd
+
+    @property
+    def boxes(self):
+        """The plan's bounds as given: ((d,), (d,)) on a shared box, ((d, S), (d, S)) on a boxed plan."""
+        if not self.boxed:
+            return self._lbs[:self.d].copy(), self._ubs[:self.d].copy()
+        shape = (self.d, self.S)
+        return self._lbs.reshape(shape, order="F").copy(), self._ubs.reshape(shape, order="F").copy()
+
+    def check_xstarts(self, xstarts, n=None):
+        """On a boxed plan the inner starts are d×n×S (n: the plan's nstarts; a base solve's own
+        count), as an array of that shape or flat column-major.  Raises ValueError otherwise; a
+        plan with a shared box takes what it always took."""
+        if not getattr(self, "boxed", False) or xstarts is None:
+            return
+        n = self.nstarts if n is None else int(n)
+        want = (self.d, n, self.S)
+        shape = tuple(xstarts.shape)
+        if shape != want and shape != (self.d * n * self.S,):
+            raise ValueError(f"a boxed plan takes inner starts d×n×S = {want}, one block per surrogate; "
+                             f"got {shape}")
 
     def close(self):
         if getattr(self, "handle", None):
@@ -142,6 +191,7 @@ class RolloutPlan:
 
     def simulate(self, x0s, rnstream, xstarts, out, dual_y_dx=None, replay_x=None, stream=None):
         """Launch mrbo_simulate_mc on device tensors (flat, column-major)."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -154,6 +204,7 @@ class RolloutPlan:
 
     def simulate_ghq(self, x0s, nodes, weights, xstarts, out, dual_y_dx=None, replay_x=None, stream=None):
         """Launch mrbo_simulate_ghq: nodes / weights are M×(h+1) device tensors (flat, column-major)."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
@@ -191,6 +242,7 @@ class RolloutPlan:
         control samples of the trajectories `simulate` runs from the same x0s and rnstream (the
         plan's full stream: its step-0 slab is read).  ctl: the dict of alloc_control (allocated
         when None; without "grad_x0" the launch takes MRBO_FLAG_NO_GRADIENT)."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         if ctl is None:
@@ -276,6 +328,7 @@ class RolloutPlan:
         plan's R restarts in one call; x0s (d·R, column-major) is updated in place, eto (W·R) and
         active (R, int32) receive the final rows and stop flags when given.  Returns (iterations
         launched, iteration after which no restart was active, OR of the status bits)."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         p = lambda t_: None if t_ is None else ctypes.c_void_p(t_.data_ptr())
@@ -290,8 +343,9 @@ class RolloutPlan:
 
     def box_adam_step(self, eto, x0s, active, m, v, t, sample_size, eta=0.02, beta1=0.9, beta2=0.999, eps=1e-8,
                       stream=None):
-        """mrbo_box_adam_step: eswavs + BoxAdam.update (mrbo/bayesopt.py) over the plan's box for every
-        active restart, in place on the device tensors of adam_step."""
+        """mrbo_box_adam_step: eswavs + BoxAdam.update (mrbo/bayesopt.py) over the plan's box -- on a
+        boxed plan the box of the restart's surrogate -- for every active restart, in place on the
+        device tensors of adam_step."""
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         p = lambda t_: ctypes.c_void_p(t_.data_ptr())
@@ -331,6 +385,7 @@ class RolloutPlan:
         Returns (xnext d·S, mean S, pick int32 S) as device tensors and the call's result (iterations
         launched, iteration after which no restart was active, status bits of the ascent, of the final
         launch); the stream is synchronised."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         dev = f"cuda:{self.device}"
@@ -348,9 +403,11 @@ class RolloutPlan:
     def rollout_solve_host(self, x0s, rnstream, xstarts, optimizer="sga", iterations=50, eta=None, beta1=0.9,
                            beta2=0.999, eps=1e-8, sample_size=0, incumbent=True, stream=None):
         """rollout_solve on numpy arrays (MRBO_FLAG_HOST_POINTERS: the library stages them once): x0s
-        d×R×S (d×R on a plain plan), rnstream M×(d+1)×(h+1), xstarts d×nstarts.  Returns a dict of
+        d×R×S (d×R on a plain plan), rnstream M×(d+1)×(h+1), xstarts d×nstarts (d×nstarts×S on a
+        boxed plan).  Returns a dict of
         numpy arrays -- x (the projected end points, x0s's shape), xnext d×S, mean S, pick S, means
         R×S, active R×S -- and `result` as rollout_solve."""
+        self.check_xstarts(xstarts)
         torch = _torch()
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         d, R, S = self.d, self.R, self.S
@@ -360,7 +417,7 @@ class RolloutPlan:
         x = np.asarray(x0s, dtype=np.float64).ravel(order="F").copy()
         rn = np.asarray(rnstream, dtype=np.float64).ravel(order="F")
         xs = np.asarray(xstarts, dtype=np.float64).ravel(order="F")
-        if rn.size != self.M * (d + 1) * (self.h + 1) or xs.size != d * self.nstarts:
+        if rn.size != self.M * (d + 1) * (self.h + 1) or xs.size != d * self.nstarts * (S if self.boxed else 1):
             raise ValueError(f"rnstream has {rn.size} entries, xstarts {xs.size}; the plan has M = {self.M}, "
                              f"h = {self.h}, {self.nstarts} inner starts")
         xnext, mean, means = np.empty(d * S), np.empty(S), np.empty(R * S)

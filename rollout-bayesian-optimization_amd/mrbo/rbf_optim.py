@@ -49,17 +49,25 @@ def base_solve_multi(surrogates, spatial_lbs, spatial_ubs, guesses, θfixed, dev
     """base_solve_batch on S base surrogates in ONE launch (a surrogate batch,
     RolloutPlan.from_surrogates): the same `guesses` (d×n) on each.  Returns (minimizers d×n×S,
     minima n×S, work counters NCOUNTERS×n×S), block q bit-identical to base_solve_batch(surrogates[q],
-    ...); raises like base_solve_batch when any surrogate's solve reports a status."""
-    from .rollout import _plan_for_multi, raise_on_status
-    torch = _torch()
+    ...); raises like base_solve_batch when any surrogate's solve reports a status.
+
+    Per-surrogate boxes: spatial_lbs, spatial_ubs of shape (d, S) and guesses d×n×S (a boxed plan);
+    block q is base_solve_batch(surrogates[q], spatial_lbs[:, q], spatial_ubs[:, q], guesses[:, :, q], ...)."""
+    from .engine import check_bounds
+    from .rollout import _plan_for_multi, check_multi_xstarts, raise_on_status
     surrogates = list(surrogates)
     S = len(surrogates)
     guesses = np.asarray(guesses, dtype=np.float64)
     if guesses.ndim == 1:
         guesses = guesses.reshape(-1, 1)
-    d, n = guesses.shape
-    if S < 1 or d != surrogates[0].X.shape[0]:
+    if S < 1 or guesses.shape[0] != surrogates[0].X.shape[0]:
         raise ValueError(f"guesses are {guesses.shape}: d×n with the d of the {S} surrogates")
+    d = guesses.shape[0]
+    boxed = check_bounds(spatial_lbs, spatial_ubs, d, S) if np.ndim(spatial_lbs) == 2 or np.ndim(spatial_ubs) == 2 \
+        else False
+    guesses = check_multi_xstarts(guesses, d, S, boxed, name="guesses")
+    n = guesses.shape[1]
+    torch = _torch()
     theta = float(np.asarray(θfixed, dtype=np.float64).ravel()[0])
     plan = _plan_for_multi(surrogates, 0, 1, 1, 1, spatial_lbs, spatial_ubs, theta, device, opts)
     dev = f"cuda:{device}"

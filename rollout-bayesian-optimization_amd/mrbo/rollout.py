@@ -62,16 +62,23 @@ def check_surrogate_batch(surrogates):
     return d, N
 
 
+def _plan_key(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts):
+    """The plan cache's key.  The bounds enter with their shape: a (d,) box is shared, the same
+    numbers as (d, S) are per-surrogate boxes -- another plan, whose calls take other xstarts."""
+    lbs, ubs = np.asarray(lbs), np.asarray(ubs)
+    return (tuple(_state_key(s) for s in ss), h, M, R, nstarts, lbs.shape, tuple(lbs.ravel(order="F")),
+            ubs.shape, tuple(ubs.ravel(order="F")), float(theta), device, tuple(sorted(opts.items())))
+
+
 def _plan_for_multi(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts):
     """The plan cache: one RolloutPlan.from_surrogates plan for the surrogates `ss`, cached on their
-    identities, versions and contents (_state_key)."""
+    identities, versions and contents (_state_key).  lbs, ubs: (d,), or (d, S) for a boxed plan."""
     check_surrogate_batch(ss)
     g = ss[0].get_decision_rule()
     opts = dict(opts)
     opts.setdefault("rule", g.rule_id)       # the surrogates' base decision rule (Q12: T.θ)
     opts.setdefault("sigma_tol", g.σtol)
-    key = (tuple(_state_key(s) for s in ss), h, M, R, nstarts, tuple(np.asarray(lbs).ravel()),
-           tuple(np.asarray(ubs).ravel()), float(theta), device, tuple(sorted(opts.items())))
+    key = _plan_key(ss, h, M, R, nstarts, lbs, ubs, theta, device, opts)
     p = _PLANS.get(key)
     if p is None:
         p = RolloutPlan.from_surrogates([surrogate_dict(s) for s in ss], h, M, R, nstarts, lbs, ubs, theta,
@@ -159,6 +166,40 @@ def check_multi_x0s(x0s, S, d=None):
     return x0s
 
 
+def per_surrogate_parameters(tp, S):
+    """`tp` of a multi call: one TrajectoryParameters shared by the S surrogates -- returns (tp, None)
+    -- or a list of S, one per surrogate, each with its own box -- returns (tp[0], (lbs, ubs)) with
+    the bounds d×S.  The S share horizon, sample count and, bit for bit, the MC stream (the launch
+    has one); a difference is a ValueError."""
+    if not isinstance(tp, (list, tuple)):
+        return tp, None
+    if len(tp) != S:
+        raise ValueError(f"{len(tp)} TrajectoryParameters for {S} surrogates")
+    t0 = tp[0]
+    for q, t in enumerate(tp[1:], start=1):
+        if t.horizon != t0.horizon or t.mc_iters != t0.mc_iters:
+            raise ValueError(f"TrajectoryParameters {q} differs from 0 in horizon or mc_iters")
+        a, b = np.asarray(t.rnstream_sequence), np.asarray(t0.rnstream_sequence)
+        if a.shape != b.shape or a.tobytes() != b.tobytes():
+            raise ValueError(f"TrajectoryParameters {q} has another rnstream_sequence than 0: the surrogates of a "
+                             "launch share the MC stream")
+    bounds = [t.get_spatial_bounds() for t in tp]
+    return t0, (np.stack([np.asarray(b[0], dtype=np.float64) for b in bounds], axis=1),
+                np.stack([np.asarray(b[1], dtype=np.float64) for b in bounds], axis=1))
+
+
+def check_multi_xstarts(xstarts, d, S, boxed, name="inner_solve_xstarts"):
+    """The inner starts (or base-solve guesses) of a multi call: d×n shared, or with per-surrogate
+    boxes d×n×S.  Raises ValueError; returns the float64 array."""
+    xs = np.asarray(xstarts, dtype=np.float64)
+    if boxed and (xs.ndim != 3 or xs.shape[0] != d or xs.shape[2] != S):
+        raise ValueError(f"{name} must be d×n×S with d = {d}, S = {S} when every surrogate has its own box; "
+                         f"got {xs.shape}")
+    if not boxed and (xs.ndim != 2 or xs.shape[0] != d):
+        raise ValueError(f"{name} must be d×n with d = {d}; got {xs.shape}")
+    return xs
+
+
 def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient=True, dual_y_dx=None,
                                  replay_x=None, want_policy=False, want_obs=False, device=0, rnstream=None,
                                  variance_reduction=False, **opts):
@@ -166,7 +207,12 @@ def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient
     kernel launch (RolloutPlan.from_surrogates): x0s is d×R×S -- R restarts per surrogate --, tp,
     the MC stream and the inner starts are shared, dual_y_dx / replay_x are d×h×M×R×S.  Returns one
     BatchResult per surrogate (views of the launch's device outputs), each bit-identical to
-    simulate_trajectory_mc_batch(Ts[q], tp, x0s[:, :, q], ...)."""
+    simulate_trajectory_mc_batch(Ts[q], tp, x0s[:, :, q], ...).
+
+    Per-surrogate boxes: tp a list of S TrajectoryParameters (their bounds the boxes, their MC
+    streams equal bit for bit) and inner_solve_xstarts d×nstarts×S.  Still one launch (a boxed
+    plan); result q is simulate_trajectory_mc_batch(Ts[q], tp[q], x0s[:, :, q],
+    inner_solve_xstarts[:, :, q], ...)."""
     import torch
     Ts = list(Ts)
     S = len(Ts)
@@ -177,7 +223,10 @@ def simulate_trajectory_mc_multi(Ts, tp, x0s, inner_solve_xstarts, with_gradient
     if any(float(T.θ[0]) != float(Ts[0].θ[0]) for T in Ts):
         raise ValueError("the trajectories of a surrogate batch share the decision-rule hyperparameter θ")
     d, R, _ = x0s.shape
-    lbs, ubs = tp.get_spatial_bounds()
+    tp, boxes = per_surrogate_parameters(tp, S)
+    lbs, ubs = tp.get_spatial_bounds() if boxes is None else boxes
+    if boxes is not None or np.ndim(inner_solve_xstarts) != 2:   # (d, n) starts on a shared box: as ever
+        inner_solve_xstarts = check_multi_xstarts(inner_solve_xstarts, d, S, boxes is not None)
     rn = tp.rnstream_sequence if rnstream is None else rnstream
     M = rn.shape[0]
     h = tp.horizon

@@ -152,12 +152,20 @@ def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iter
     restart keeps its own optimizer state and eswavs stop flag, so surrogate q's restarts move
     exactly as stochastic_solve_batch(optimizers[q], surrogates[q], tp, es, starts[:, :, q]) moves
     them.  variance_reduction=True: every iteration's ETO rows are the control-variate ones (DESIGN.md
-    §16).  Returns (x d×R×S, history: per iteration, per surrogate, the R ETOs)."""
-    from .rollout import check_multi_x0s, simulate_trajectory_mc_multi
+    §16).  Returns (x d×R×S, history: per iteration, per surrogate, the R ETOs).
+
+    Per-surrogate boxes: tp and es lists of S (simulate_trajectory_mc_multi), each surrogate's inner
+    starts its own ExperimentSetup's; still one launch per iteration."""
+    from .rollout import check_multi_x0s, per_surrogate_parameters, simulate_trajectory_mc_multi
     from .surrogates import FantasySurrogate
     from .trajectory import Trajectory
     surrogates = list(surrogates)
     S = len(surrogates)
+    tps = tp
+    tp, boxes = per_surrogate_parameters(tps, S)
+    if (boxes is None) != (not isinstance(es, (list, tuple))) or (boxes is not None and len(es) != S):
+        raise ValueError("tp and es are both shared or both lists of one per surrogate")
+    xstarts = es.get_starts() if boxes is None else np.stack([e.get_starts() for e in es], axis=2)
     x = np.array(check_multi_x0s(starts, S), dtype=np.float64)
     d, R, _ = x.shape
     if len(optimizers) != S or any(len(o) != R for o in optimizers):
@@ -172,7 +180,7 @@ def stochastic_solve_multi(optimizers, surrogates, tp, es, starts, Ts=None, iter
     for _ in range(iterations):
         if not active.any():
             break
-        brs = simulate_trajectory_mc_multi(Ts, tp, x, es.get_starts(), device=device,
+        brs = simulate_trajectory_mc_multi(Ts, tps, x, xstarts, device=device,
                                            variance_reduction=variance_reduction, **opts)
         etos = [br.etos() for br in brs]
         history.append(etos)
